@@ -7,11 +7,20 @@ d_model=1024, H=4, dropout 0.1 in train mode (BASELINE.json configs[1]).  Inputs
 region.  One process per GPU (RCCL all-reduce of the flat gradient bucket): for N > 1 launch with torch.distributed.run, or
 just `python bench.py --gpus N` -- without WORLD_SIZE in the environment the script starts its N ranks itself.
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+Prints ONE JSON line on rank 0 with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+A plain run does only that: set up, warm up, time --steps steps, write the outputs (--dump-outputs DIR), print the line.
+With --full the line also holds
   roofline     -- the cross-modal attention kernels (V<-A: B16 H4 Sq256 Sk800; A<-V: Sq800 Sk256) with the step's padded
                   masks: flops EXECUTED per launch / mean launch time measured here with HIP events on the launch
                   stream, vs the 2.5 PFLOP/s dense bf16 MFMA peak (attention_roofline()),
-  cpu_baseline -- the CPU oracle (oracle/, a port of the reference's arithmetic) timed on this host on a bounded sample.
+  cpu_baseline -- the CPU oracle (oracle/, a port of the reference's arithmetic) timed on this host on a bounded sample;
+without --full both are null.
+
+--dump-outputs DIR writes what the last timed step hands its caller (dump_outputs()): DIR/loss.npy (float64) and
+DIR/params.npy (float32, the updated weights; a fixed seeded sample of them).  The inputs, weights and dropout seeds are
+fixed by the arguments, so two builds run with the same arguments can be compared output for output.  By default the
+fp32 atomic sums make two runs agree to rounding only (Adam's update of weights whose gradient is near zero magnifies
+that); with BMHRL_DETERMINISTIC=1 they agree bit for bit.
 """
 import argparse
 import json
@@ -47,7 +56,15 @@ def parse():
     ap.add_argument("--no-exploration", action="store_true",
                     help="A/B aid: the manager's exploration noise off (the reference's warmstart step has it ON, the default here)")
     ap.add_argument("--cpu-batch", type=int, default=16, help="batch of the bounded CPU-oracle sample (default: the full B=16 step)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the secondary figures: the attention roofline and the CPU-oracle baseline "
+                         "(off: a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (loss, sampled updated weights)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _time_launches(fn, iters):
@@ -236,6 +253,30 @@ def cpu_baseline(args):
                       f"linearly to B={args.batch}"}
 
 
+DUMP_PARAMS = 1 << 23        # at most 8 M weights (32 MB of float32) in params.npy
+
+
+def dump_outputs(path, trainer, loss):
+    """What a caller of the timed step receives after its last call: the loss it returns and the weights it updated.
+      loss.npy   -- float64 (1,)
+      params.npy -- float32: every parameter of the agent (and of the value head in --mode rl), flattened and concatenated
+                    in state-dict name order; when there are more than DUMP_PARAMS of them, a fixed sample of DUMP_PARAMS
+                    positions (seed 0, ascending, drawn with replacement) of that concatenation"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    mods = [("agent.", trainer.agent)] + ([("value_net.", trainer.value_net)] if trainer.value_net is not None else [])
+    named = sorted(((pre + n, p) for pre, m in mods for n, p in m.named_parameters()), key=lambda t: t[0])
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for _, p in named])
+        if flat.numel() > DUMP_PARAMS:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randint(0, flat.numel(), (DUMP_PARAMS,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        params = flat.cpu().numpy().astype(np.float32)
+    np.save(os.path.join(path, "loss.npy"), np.array([float(loss)], dtype=np.float64))
+    np.save(os.path.join(path, "params.npy"), params)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` without a launcher (the reference needs none either: nn.DataParallel,
     scripts/train_rl_captioning_module.py:95-99): start the N ranks as children under torch.distributed.run -- before this
@@ -329,8 +370,10 @@ def main():
     loss_v = float(loss)
 
     if rank == 0:
-        roof = attention_roofline(dev, args.batch, cfg.rl_att_heads, args.tv, args.ta)
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(args)   # N=1 only (bench contract)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, trainer, loss)
+        roof = attention_roofline(dev, args.batch, cfg.rl_att_heads, args.tv, args.ta) if args.full else None
+        cpu = None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(args)   # N=1 only (bench contract)
         out = {
             "metric": "caption-train steps/sec", "value": args.steps * world / elapsed, "unit": "steps/s (one step = one "
             "B=16 batch on one GPU; whole-job aggregate over all GPUs)", "n_gpus": world, "steps": args.steps,

@@ -3,7 +3,7 @@
 #   1. rocprofv3 --kernel-trace --stats of the attention kernels alone, of the eager step and of the bench command itself
 #   2. counter-only passes (separate runs, no trace domains) of the two cross-modal attention launches: MFMA busy cycles,
 #      wave cycles, waits; FETCH_SIZE / WRITE_SIZE of the V<-A launch
-#   3. the default bench.py line
+#   3. the bench.py line with --full (roofline + CPU baseline)
 R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/round
 rm -rf $OUT; mkdir -p $OUT
@@ -20,12 +20,12 @@ run pmc128a rocprofv3 --pmc $P1 --output-format csv -d $OUT/pmc128a -- python3 $
 run pmc128b rocprofv3 --pmc $P2 --output-format csv -d $OUT/pmc128b -- python3 $R/tests/bench_one_attn128.py
 SQ=800 SK=256 run pmc256a rocprofv3 --pmc $P1 --output-format csv -d $OUT/pmc256a -- python3 $R/tests/bench_one_attn.py
 SQ=800 SK=256 run pmc256b rocprofv3 --pmc $P2 --output-format csv -d $OUT/pmc256b -- python3 $R/tests/bench_one_attn.py
-run eager rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/eager -- python3 $R/bench.py --eager --steps 8 --warmup 2 --no-cpu-baseline
+run eager rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/eager -- python3 $R/bench.py --eager --steps 8 --warmup 2 --no-cpu-baseline --full
 # the bench command itself under the tracer (graph mode): its last phase launches the roofline kernel in isolation
-run benchtrace rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/benchtrace -- python3 $R/bench.py --no-cpu-baseline
+run benchtrace rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/benchtrace -- python3 $R/bench.py --no-cpu-baseline --full
 cd $R
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -3 $OUT/bench.err; exit 1; }
-python3 bench.py --mode rl --no-cpu-baseline > $OUT/bench_rl.json 2> $OUT/bench_rl.err || { tail -3 $OUT/bench_rl.err; exit 1; }
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -3 $OUT/bench.err; exit 1; }
+python3 bench.py --mode rl --no-cpu-baseline --full > $OUT/bench_rl.json 2> $OUT/bench_rl.err || { tail -3 $OUT/bench_rl.err; exit 1; }
 python3 profiles/bench_trace_summary.py $OUT/benchtrace $OUT/benchtrace.log > $OUT/bench_kernel_stats.md
 python3 profiles/summarize.py $OUT/eager 10 > $OUT/eager_stats.md
 python3 - <<PY > $OUT/attn_summary.txt
