@@ -10,6 +10,8 @@ Three forms, same tokens:
     layer keeps the K|V rows of the tokens decoded so far, the frozen critic carries its LSTM / GRU state, and a token costs
     one row per sample through both fusion stacks, the manager and the worker.  All shapes of a token step are static, the
     position is a device word, so the step is captured once into a HIP graph and replayed max_len times.
+
+beam_decode / beam_decoder: beam search over the same token step on B*K rows (BeamDecoder), or over full re-runs.
 """
 import math
 
@@ -104,9 +106,13 @@ class IncrementalDecoder:
             dec = cache[key] = cls(agent, *key[:7], device=key[7])
         return dec
 
-    def __init__(self, agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device):
+    def __init__(self, agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device, beams=1):
         self.agent = agent
         self.B, self.tv_cap, self.ta_cap, self.max_len = B, tv_cap, ta_cap, max_len
+        # rows of every token-dependent buffer: `beams` consecutive rows per sample (BeamDecoder); the per-clip memory K|V and
+        # its masks keep one row per sample, and its attentions take a sample's rows as `beams` queries
+        self.K = beams
+        self.R = R = B * beams
         self.start_idx, self.end_idx, self.pad_idx = start_idx, end_idx, pad_idx
         self.dev = dev = torch.device(device)
         self.dC, self.D = agent.d_model_caps, agent.d_model
@@ -114,24 +120,24 @@ class IncrementalDecoder:
         D, dC = self.D, self.dC
         z = lambda *s, dtype=torch.float32: torch.zeros(*s, dtype=dtype, device=dev)
         self.t = z(1, dtype=torch.int64)
-        self.tok = z(B, dtype=torch.int64)
-        self.out = z(B, max_len + 1, dtype=torch.int64)
-        self.done = z(B, dtype=torch.bool)
-        self.valid = z(B, 1, Lc, dtype=torch.uint8)
+        self.tok = z(R, dtype=torch.int64)
+        self.out = z(R, max_len + 1, dtype=torch.int64)
+        self.done = z(R, dtype=torch.bool)
+        self.valid = z(R, 1, Lc, dtype=torch.uint8)
         self.a_mask = z(B, 1, ta_cap, dtype=torch.uint8)
         self.v_mask = z(B, 1, tv_cap, dtype=torch.uint8)
-        self.labels = z(B, Lc, dtype=torch.int32)
-        self.goals_raw = z(B, Lc, agent.d_goal)
-        self.logp = z(B, 1, agent.voc_size)
+        self.labels = z(R, Lc, dtype=torch.int32)
+        self.goals_raw = z(R, Lc, agent.d_goal)
+        self.logp = z(R, 1, agent.voc_size)
         self.emb_scale = math.sqrt(dC)
         self.pe = agent.pos_enc_C.table(dev)
         n_layers = len(agent.bm_worker_fus.decoder.layers)
-        mk = lambda rows: z(B, rows, 2 * D, dtype=_BF16)
+        mk = lambda n, rows: z(n, rows, 2 * D, dtype=_BF16)
         self.stacks = []
         for fus in (agent.bm_worker_fus, agent.bm_manager_fus):
-            self.stacks.append(dict(fus=fus, self_kv=[mk(Lc) for _ in range(n_layers)],
-                                    mem_a=[mk(ta_cap) for _ in range(n_layers)], mem_v=[mk(tv_cap) for _ in range(n_layers)]))
-        self.goal_kv = z(B, Lc, 2 * agent.worker.goal_attention.d_model, dtype=_BF16)
+            self.stacks.append(dict(fus=fus, self_kv=[mk(R, Lc) for _ in range(n_layers)],
+                                    mem_a=[mk(B, ta_cap) for _ in range(n_layers)], mem_v=[mk(B, tv_cap) for _ in range(n_layers)]))
+        self.goal_kv = z(R, Lc, 2 * agent.worker.goal_attention.d_model, dtype=_BF16)
         cr = agent.critic
         Hc = cr.lstm.hidden_size
         self.critic_layers = []
@@ -140,21 +146,25 @@ class IncrementalDecoder:
                 self.critic_layers.append(dict(
                     gates=gates, w_ih=getattr(rnn, f"weight_ih_l{l}"), w_hh=getattr(rnn, f"weight_hh_l{l}"),
                     b_ih=getattr(rnn, f"bias_ih_l{l}"), b_hh=getattr(rnn, f"bias_hh_l{l}"),
-                    act=act if l == n - 1 else None, h=z(B, Hc), c=z(B, Hc), h_new=z(B, Hc), c_new=z(B, Hc),
+                    act=act if l == n - 1 else None, h=z(R, Hc), c=z(R, Hc), h_new=z(R, Hc), c_new=z(R, Hc),
                     # the step kernel reads the carried state only at positions > 0 of its window: the newest token is
                     # position 1 of a two-position window whose position 0 is never touched
-                    xproj=z(B, 2, gates * Hc), seq=z(B, 2, Hc)))
-        self.labels2 = z(B, 2, dtype=torch.int32)
+                    xproj=z(R, 2, gates * Hc), seq=z(R, 2, Hc)))
+        self.labels2 = z(R, 2, dtype=torch.int32)
         self.Hc = Hc
         self.graph = None
         self._shadow_sig = None
         self.steps_run = 0
+        self._init_search()
         with torch.no_grad():
             self._reset()
             self._token_step()                      # eager once: weight shadows, allocator warm-up
             if self.use_graph:
                 self._capture()
             self._reset()
+
+    def _init_search(self):
+        """buffers of the token choice (greedy: none beyond `out` / `done`)"""
 
     # ------------------------------------------------------------------ per clip
     def _reset(self):
@@ -262,10 +272,11 @@ class IncrementalDecoder:
         self.graph = g
 
     # ------------------------------------------------------------------ one token
-    def _attend(self, att, norm, x, kv, mask, Sk, residual, append):
-        """x (B, dq) fp32 -> [x +] d2Q(attention(Q2d(LN?(x)), K|V rows in `kv`)) (B, dq) fp32.  append: this is a self
-        attention -- the K|V projection of the (normalised) row is written at position t of `kv` first."""
-        B, dev = self.B, self.dev
+    def _attend(self, att, norm, x, kv, mask, Sk, residual, append, sq=1):
+        """x (R, dq) fp32 -> [x +] d2Q(attention(Q2d(LN?(x)), K|V rows in `kv`)) (R, dq) fp32.  append: this is a self
+        attention -- the K|V projection of the (normalised) row is written at position t of `kv` first.  sq: query rows per
+        batch entry of `kv` (the per-sample memory: the sample's beams; 1: one K|V batch entry per row)."""
+        B, dev = self.R, self.dev
         D, H = att.d_model, att.H
         dq = x.shape[1]
         ldx = pad8(dq)
@@ -287,7 +298,7 @@ class IncrementalDecoder:
             q = torch.empty(B, D, dtype=_BF16, device=dev)
             ops.gemm(xb, w, B, D, dq, lda=ldx, ldb=w.shape[1], C_bf16=q, ldcb=D, bias=att.linear_Q2d.bias.detach())
             ldq = D
-        o, _ = _attn_core_fwd(q, 0, ldq, kv, 0, 2 * D, kv, D, 2 * D, mask, Sk, 0, B, H, 1, Sk, D // H, 0.0, 0)
+        o, _ = _attn_core_fwd(q, 0, ldq, kv, 0, 2 * D, kv, D, 2 * D, mask, Sk, 0, B // sq, H, sq, Sk, D // H, 0.0, 0)
         w_o = SHADOWS.weight(att.linear_d2Q.weight)
         y = torch.empty(B, dq, device=dev)
         ops.gemm(o, w_o, B, dq, D, lda=D, ldb=w_o.shape[1], C_f32=y, ldc=dq, bias=att.linear_d2Q.bias.detach(),
@@ -295,7 +306,7 @@ class IncrementalDecoder:
         return y
 
     def _critic_step(self, emb):
-        B, Hc = self.B, self.Hc
+        B, Hc = self.R, self.Hc
         x = emb
         for l in self.critic_layers:
             g = l["gates"]
@@ -313,7 +324,7 @@ class IncrementalDecoder:
         self.labels.index_copy_(1, self.t, self.labels2[:, 1:2])
 
     def _token_step(self):
-        ag, B, t = self.agent, self.B, self.t
+        ag, B, t = self.agent, self.R, self.t
         emb = ag.emb_C.embedder.weight.detach().index_select(0, self.tok) * self.emb_scale     # (B, dC): the critic's input
         C0 = emb + self.pe.index_select(0, t)
         self.valid.index_copy_(2, t, (self.tok != self.pad_idx).to(torch.uint8).view(B, 1, 1))
@@ -326,9 +337,9 @@ class IncrementalDecoder:
                 C = self._attend(a, layer.res_layer_self_att.norm, C, st["self_kv"][li], self.valid, self.Lc, True,
                                  ((a.linear_K2d.weight, a.linear_V2d.weight), (a.linear_K2d.bias, a.linear_V2d.bias)))
                 Ca = self._attend(layer.enc_att_A, layer.res_layer_enc_att_A.norm, C, st["mem_a"][li], self.a_mask, self.ta_cap,
-                                  True, None)
+                                  True, None, self.K)
                 Cv = self._attend(layer.enc_att_V, layer.res_layer_enc_att_V.norm, C, st["mem_v"][li], self.v_mask, self.tv_cap,
-                                  True, None)
+                                  True, None, self.K)
                 C = layer._tail(Cv, Ca)            # normCA, normCV, gate: the kernel of the full forward (bit-identical)
             feats.append(C)
         w_feat, m_feat = feats
@@ -349,8 +360,209 @@ class IncrementalDecoder:
         logp = WorkerHeadFn.apply(w_feat.view(B, 1, -1), gc.view(B, 1, -1), ag.worker.core.projection.weight,
                                   ag.worker.core.projection.bias)
         self.logp.copy_(logp)
+        self._choose(logp)
+        t.add_(1)
+
+    def _choose(self, logp):
+        """greedy: the arg-max token of every row is the next input"""
+        B, t = self.R, self.t
         nxt = logp.view(B, -1).argmax(-1)
         self.out.index_copy_(1, t + 1, nxt.view(B, 1))
         self.done.logical_or_(nxt == self.end_idx)
         self.tok.copy_(nxt)
-        t.add_(1)
+
+
+# ---------------------------------------------------------------------------------------------------------- beam search
+# Rules (both paths below implement exactly these):
+#  1. beam 0 of a sample starts live with score 0 and input start_idx; beams 1..K-1 start finished with score -inf;
+#  2. at every step a live beam k offers V candidates (k, v) scored score_k + lp(k, v) (one fp32 add), a finished beam the
+#     single candidate (k, pad_idx) with score_k;
+#  3. per sample the K best candidates become the new beams, best first, ties to the smaller k*V + v (a stable sort of
+#     -score); choosing end_idx finishes a beam;
+#  4. stop after the step at which every beam of every sample is finished, or after max_len steps;
+#  5. n_k = generated tokens up to and including the first end_idx (the steps run if none); the best hypothesis has the
+#     largest score_k / ((5 + n_k) / 6) ** length_penalty, ties to the lower beam index;
+#  6. the result is int64 (B, n + 1): start_idx, the chosen hypothesis, pad_idx after its end; n = max n_k of the chosen.
+# With K = 1 this is greedy decoding with pad_idx after each sample's first end_idx (up to candidates whose fp32 sums
+# round to the same score: rule 3 then takes the smaller token id).
+
+
+def beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, beam_size=4, length_penalty=0.0,
+                return_scores=False, return_beams=False, incremental=None):
+    """Beam search with the reference decoder's arguments.  Returns tokens (B, n + 1) int64, then -- when asked -- the
+    chosen hypotheses' raw scores (B,) fp32, then all K hypotheses sorted best first as tokens (B, K, m + 1) (m: the
+    longest n_k of all of them, so that no hypothesis is cut) and raw scores (B, K).
+    incremental (default: on under the conditions greedy_decode takes IncrementalDecoder, and K <= min(16, V)) decodes
+    through BeamDecoder; otherwise, or with incremental=False, every step re-runs model.inference over the (B*K)-row prefix
+    batch (any model with `inference`, CPU included)."""
+    K = int(beam_size)
+    if K < 1:
+        raise ValueError(f"beam_size must be >= 1, got {beam_size}")
+    with torch.no_grad():
+        device = feature_stacks['audio'].device
+        if incremental is None:
+            incremental = BeamDecoder.enabled
+        found = None
+        if (incremental and hasattr(model, "encode_memory") and not model.training and device.type == "cuda"
+                and modality == "audio_video" and max_len >= 1 and K <= min(ops.BEAM_MAX, getattr(model, "voc_size", 0))):
+            dec = BeamDecoder.for_batch(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, K)
+            if dec.begin(feature_stacks):
+                found = dec.run()
+        if found is None:
+            found = _beam_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, K)
+        return _beam_result(*found, end_idx, length_penalty, return_scores, return_beams)
+
+
+def beam_decoder(beam_size=4, length_penalty=0.0):
+    """a decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality), e.g.
+    validation_1by1_loop(cfg, model, loader, beam_decoder(4), epoch, TBoard)"""
+    if int(beam_size) < 1:
+        raise ValueError(f"beam_size must be >= 1, got {beam_size}")
+
+    def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
+        return beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, beam_size=beam_size,
+                           length_penalty=length_penalty)
+    return decoder
+
+
+def _beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K):
+    """rules 1-4 over full re-runs of model.inference on the prefix batch -> (tokens (B, K, n + 1), scores (B, K), n)"""
+    B = fs['audio'].shape[0]
+    dev = fs['audio'].device
+    rep = {k: v.repeat_interleave(K, 0) if torch.is_tensor(v) and v.dim() and v.shape[0] == B else v for k, v in fs.items()}
+    x = ((rep['rgb'], rep['flow']), rep['audio'])
+    scores = torch.full((B, K), float("-inf"), device=dev)
+    scores[:, 0] = 0.0
+    finished = torch.ones(B, K, dtype=torch.bool, device=dev)
+    finished[:, 0] = False
+    hist = torch.full((B * K, 1), start_idx, dtype=torch.long, device=dev)
+    steps = 0
+    while steps < max_len:
+        lp = model.inference(x, hist, make_masks(rep, hist, modality, pad_idx))[:, -1].float()
+        V = lp.shape[-1]
+        cand = scores.unsqueeze(-1) + lp.view(B, K, V)
+        only = torch.zeros_like(cand)
+        only[..., pad_idx] = scores
+        cand = torch.where(finished.unsqueeze(-1), only, cand).view(B, K * V)
+        pick = _stable_top(cand, finished, pad_idx)
+        parent, tok = pick // V, pick % V
+        scores = cand.gather(1, pick)
+        finished = finished.gather(1, parent) | (tok == end_idx)
+        hist = hist.view(B, K, -1).gather(1, parent.unsqueeze(-1).expand(-1, -1, hist.shape[-1])).view(B * K, -1)
+        hist = torch.cat([hist, tok.view(B * K, 1)], 1)
+        steps += 1
+        if bool(finished.all()):
+            break
+    return hist.view(B, K, -1), scores, steps
+
+
+def _stable_top(cand, finished, pad_idx):
+    """flat indices of the K best of the (B, K*V) candidates per sample, ties to the smaller index; the V - 1 entries of a
+    finished beam other than (k, pad_idx) are not candidates.  Two stable sorts (score, then candidate-or-not) instead of a
+    NaN filler: where NaN sorts depends on the device's sort."""
+    B, K = finished.shape
+    V = cand.shape[1] // K
+    excluded = finished.unsqueeze(-1) & (torch.arange(V, device=cand.device) != pad_idx)
+    by_score = torch.sort(-cand, dim=1, stable=True).indices
+    by_kind = torch.sort(excluded.view(B, K * V).gather(1, by_score).to(torch.uint8), dim=1, stable=True).indices
+    return by_score.gather(1, by_kind)[:, :K]
+
+
+def _beam_result(toks, scores, steps, end_idx, length_penalty, return_scores, return_beams):
+    """rules 5-6 over (B, K, >= steps + 1) hypotheses and their raw scores"""
+    B, K = scores.shape
+    toks = toks[..., :steps + 1]
+    is_end = toks[..., 1:] == end_idx
+    before = (is_end.cumsum(-1) == 0).sum(-1)
+    n_k = torch.where(is_end.any(-1), before + 1, torch.full_like(before, steps))
+    final = scores / ((5.0 + n_k.to(scores.dtype)) / 6.0) ** length_penalty
+    order = torch.sort(-final, dim=1, stable=True).indices
+    rows = torch.arange(B, device=scores.device)
+    best = order[:, 0]
+    n = int(n_k[rows, best].max()) if B else 0
+    out = [toks[rows, best, :n + 1].clone()]
+    if return_scores:
+        out.append(scores[rows, best].clone())
+    if return_beams:
+        m = int(n_k.max()) if B else 0
+        out += [toks.gather(1, order.unsqueeze(-1).expand(-1, -1, toks.shape[-1]))[..., :m + 1].clone(), scores.gather(1, order)]
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+class BeamDecoder(IncrementalDecoder):
+    """IncrementalDecoder's token step on B*K rows (sample-major: the K beams of a sample are consecutive rows), followed
+    by the HIP beam step inside the same captured graph:
+
+      bmhrl_beam_select   per sample, the K best of the K*V candidates (rules 2-3): new scores, finished flags, parents,
+                          next input tokens, history column t + 1, and the `last_live` word the host polls;
+      bmhrl_beam_reorder  rows [0, t] of every per-beam buffer (caption self K|V of both stacks, goal K|V, the 12 critic
+                          h / c tensors, labels, raw goals, the valid mask, the token history) from the parent beam, as a
+                          gather into a scratch image and a copy-back (two launches over one table of buffers).
+
+    The per-clip memory K|V is not replicated: its attentions take a sample's K beam rows as K queries."""
+
+    _cache_attr = "_beam_decoders"
+
+    @classmethod
+    def for_batch(cls, agent, fs, max_len, start_idx, end_idx, pad_idx, beam_size=4):
+        B, Tv = fs['rgb'].shape[:2]
+        Ta = fs['audio'].shape[1]
+        key = (B, -(-Tv // 64) * 64, -(-Ta // 64) * 64, int(max_len), int(start_idx), int(end_idx), int(pad_idx),
+               int(beam_size), fs['rgb'].device)
+        cache = agent.__dict__.setdefault(cls._cache_attr, {})
+        dec = cache.get(key)
+        if dec is None:
+            if len(cache) >= 8:
+                cache.pop(next(iter(cache)))
+            dec = cache[key] = cls(agent, *key[:7], device=key[8], beams=key[7])
+        return dec
+
+    def __init__(self, agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device, beams=4):
+        if not 1 <= beams <= min(ops.BEAM_MAX, agent.voc_size):
+            raise ValueError(f"BeamDecoder: beam size {beams} outside [1, min(16, V)]")
+        super().__init__(agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device, beams=beams)
+
+    def _init_search(self):
+        R, dev = self.R, self.dev
+        self.scores = torch.zeros(R, device=dev)
+        self.finished = torch.zeros(R, dtype=torch.uint8, device=dev)
+        self.parent = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.last_live = torch.zeros(1, dtype=torch.int32, device=dev)
+        per_beam = [(kv, kv[0, 0].numel() * kv.element_size()) for st in self.stacks for kv in st["self_kv"]]
+        per_beam += [(self.goal_kv, self.goal_kv[0, 0].numel() * self.goal_kv.element_size())]
+        per_beam += [(l[k], 0) for l in self.critic_layers for k in ("h", "c")]
+        per_beam += [(self.labels, 4), (self.goals_raw, self.goals_raw.shape[-1] * 4), (self.valid, 1), (self.out, 8)]
+        self._scratch = [torch.empty_like(b) for b, _ in per_beam]
+        self._table, self._n_blocks = ops.beam_reorder_table(
+            [(b, s, pos) for (b, pos), s in zip(per_beam, self._scratch)], R, dev)
+        self._n_buffers = len(per_beam)
+
+    def _reset(self):
+        super()._reset()
+        s, f = self.scores.view(self.B, self.K), self.finished.view(self.B, self.K)
+        s.fill_(float("-inf")); s[:, 0] = 0.0
+        f.fill_(1); f[:, 0] = 0
+        self.parent.zero_()
+        self.last_live.zero_()
+
+    def _choose(self, logp):
+        V = self.logp.shape[-1]
+        ops.beam_select(self.logp, V, self.scores, self.finished, self.parent, self.tok, self.out, self.t, self.last_live,
+                        self.B, self.K, V, self.end_idx, self.pad_idx)
+        for phase in (0, 1):
+            ops.beam_reorder(self._table, self._n_buffers, self._n_blocks, self.parent, self.R, self.K, self.t, phase)
+
+    def run(self):
+        """-> (tokens (B, K, n + 1), raw scores (B, K), n): the beams after the step at which every beam had finished"""
+        for i in range(self.max_len):
+            self.step()
+            if (i + 1) % self.check_every == 0 and i + 1 < self.max_len and int(self.last_live) < i + 1:
+                break
+        n = self.steps_run
+        last = int(self.last_live)
+        if last < n:
+            n = last + 1
+        return self.out[:, :n + 1].view(self.B, self.K, n + 1).clone(), self.scores.view(self.B, self.K).clone(), n
+
+    def result(self):
+        raise NotImplementedError("BeamDecoder: use run() (or beam_decode)")

@@ -13,7 +13,7 @@ import random
 
 import torch
 
-from ..decode import greedy_decode
+from ..decode import beam_decoder, greedy_decode  # noqa: F401  (beam_decoder: a decoder for the validation loops)
 from ..model.masking import make_masks
 
 

@@ -637,3 +637,62 @@ def groupnorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, B, T, C, G):
     _need_cuda(dy, x, dx)
     _lib.check(_lib.load().bmhrl_groupnorm_bwd(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                                dx.data_ptr(), _p(dgamma), _p(dbeta), B, T, C, G, stream()), "bmhrl_groupnorm_bwd")
+
+
+# ---- beam-search decoding (csrc/beam.hip)
+BEAM_MAX = 16                       # largest beam of bmhrl_beam_select
+BEAM_REORDER_CHUNK = 256 * 16 * 4   # bytes of one (buffer, row) a reorder workgroup moves
+
+
+def beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_live, B, K, V, end_idx, pad_idx,
+                scores_out=None, finished_out=None):
+    """per sample, the K best candidates of rule 3 (see bmhrl_beam_select in include/bmhrl_hip.h): scores (B*K) fp32 and
+    finished (B*K) uint8 are updated in place unless *_out are given; parent (B*K) int32, tok (B*K) int64,
+    hist (B*K, cols) int64 column t + 1, last_live (1,) int32 = t + 1 when a beam is still live.  t: (1,) int64 device word."""
+    _need_cuda(logp, scores, finished, parent, tok, hist, t, last_live)
+    scores_out = scores if scores_out is None else scores_out
+    finished_out = finished if finished_out is None else finished_out
+    R = B * K
+    if not (1 <= K <= BEAM_MAX and K <= V and ld >= V and logp.dtype == torch.float32 and logp.numel() >= (R - 1) * ld + V):
+        raise ValueError("beam_select: need 1 <= K <= 16, K <= V and fp32 logp rows (B*K, ld >= V)")
+    for x, dt in ((scores, torch.float32), (scores_out, torch.float32), (finished, torch.uint8), (finished_out, torch.uint8),
+                  (parent, torch.int32), (tok, torch.int64)):
+        if x.dtype != dt or x.numel() < R or not x.is_contiguous():
+            raise ValueError(f"beam_select: expected a contiguous {dt} buffer of {R} elements")
+    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != R or hist.stride(1) != 1:
+        raise ValueError("beam_select: hist must be (B*K, cols) int64 with contiguous rows")
+    if t.dtype != torch.int64 or last_live.dtype != torch.int32:
+        raise ValueError("beam_select: t is an int64 word, last_live an int32 word")
+    _lib.check(_lib.load().bmhrl_beam_select(logp.data_ptr(), ld, scores.data_ptr(), finished.data_ptr(), scores_out.data_ptr(),
+                                             finished_out.data_ptr(), parent.data_ptr(), tok.data_ptr(), hist.data_ptr(),
+                                             hist.stride(0), hist.shape[1], t.data_ptr(), last_live.data_ptr(), B, K, V, end_idx,
+                                             pad_idx, stream()), "bmhrl_beam_select")
+
+
+def beam_reorder_table(buffers, rows, device):
+    """[(state, scratch, pos_bytes)] -> (device table of bmhrl_beam_buffer entries, n_blocks) for beam_reorder.  state and
+    scratch: contiguous tensors of the same shape whose first axis is the beam row; pos_bytes: bytes of one position of a
+    row (0: no position axis, the whole row moves)."""
+    words = []
+    n_blocks = 0
+    for state, scratch, pos_bytes in buffers:
+        if (state.shape != scratch.shape or state.dtype != scratch.dtype or not state.is_contiguous() or not scratch.is_contiguous()
+                or state.shape[0] != rows):
+            raise ValueError("beam_reorder_table: state and scratch must be contiguous, alike and have one row per beam")
+        beam_bytes = state.numel() // rows * state.element_size()
+        if pos_bytes < 0 or pos_bytes > beam_bytes:
+            raise ValueError("beam_reorder_table: pos_bytes out of range")
+        words += [state.data_ptr(), scratch.data_ptr(), beam_bytes, pos_bytes]
+        n_blocks += rows * (-(-beam_bytes // BEAM_REORDER_CHUNK))
+    table = torch.tensor(words, dtype=torch.int64).to(device)
+    return table, n_blocks
+
+
+def beam_reorder(table, n_buffers, n_blocks, parent, rows, K, t, phase):
+    """phase 0: scratch[j] = rows [0, t] of state[parent row of j]; phase 1: state[j] = scratch[j] (rows j whose parent is
+    themselves are skipped in both); see bmhrl_beam_reorder in include/bmhrl_hip.h"""
+    _need_cuda(table, parent, t)
+    if table.dtype != torch.int64 or table.numel() != 4 * n_buffers or parent.dtype != torch.int32 or parent.numel() < rows:
+        raise ValueError("beam_reorder: table of n_buffers x 4 int64 words and an int32 parent per row expected")
+    _lib.check(_lib.load().bmhrl_beam_reorder(table.data_ptr(), n_buffers, n_blocks, parent.data_ptr(), rows, K, t.data_ptr(),
+                                              phase, stream()), "bmhrl_beam_reorder")

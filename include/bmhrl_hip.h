@@ -510,6 +510,32 @@ int bmhrl_groupnorm_fwd(const float* x, const float* gamma, const float* beta, f
 int bmhrl_groupnorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd, float* dx,
                         float* dgamma, float* dbeta, int32_t B, int32_t T, int32_t C, int32_t G, bmhrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Beam-search caption decoding (bmhrl_amd/decode.py BeamDecoder: B samples x K beams, rows sample-major).  Both read the
+ * step position t from a device word (a captured token step replays them unchanged).
+ *  bmhrl_beam_select: per sample, the K best of the candidates (k, v) with score_k + logp[k][v] (live beam k) or (k, pad)
+ *    with score_k (finished beam k), best first, ties to the smaller k*V + v.  Writes the new scores and finished flags
+ *    (finished = parent finished or v == end_idx; the outputs may alias the inputs), the parent beam (0..K-1 within the
+ *    sample), the next input token, hist[row][t + 1] (when t + 1 < hist_cols), and last_live[0] = t + 1 when any new
+ *    beam is live.  1 <= K <= 16, K <= V.
+ *  bmhrl_beam_reorder: for every table entry and every row j whose parent is not itself, exactly the first
+ *    min(beam_bytes, (t + 1) * pos_bytes) bytes of row j (pos_bytes = 0: the whole row) take the parent row's: phase 0
+ *    copies state[parent row] -> scratch[j], phase 1 scratch[j] -> state[j]; the rest of the row is not touched.
+ *    n_blocks = sum over entries of rows * ceil(beam_bytes / 16384).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct bmhrl_beam_buffer {
+  void* state;          /* (rows, beam_bytes) per-beam buffer */
+  void* scratch;        /* the same size: the gathered rows between the two phases */
+  int64_t beam_bytes;   /* bytes per beam row */
+  int64_t pos_bytes;    /* bytes per position of the row; 0: no position axis */
+} bmhrl_beam_buffer;
+int bmhrl_beam_select(const float* logp, int64_t ld, const float* scores_in, const uint8_t* finished_in, float* scores_out,
+                      uint8_t* finished_out, int32_t* parent, int64_t* tok, int64_t* hist, int64_t ldh, int32_t hist_cols,
+                      const int64_t* t, int32_t* last_live, int32_t B, int32_t K, int32_t V, int32_t end_idx,
+                      int32_t pad_idx, bmhrl_stream_t stream);
+int bmhrl_beam_reorder(const bmhrl_beam_buffer* table, int32_t n_buffers, int64_t n_blocks, const int32_t* parent,
+                       int32_t rows, int32_t K, const int64_t* t, int32_t phase, bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
