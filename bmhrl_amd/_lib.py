@@ -160,6 +160,10 @@ def load() -> C.CDLL:
     lib.bmhrl_small_attention_ok.restype = C.c_int
     lib.bmhrl_gemm_splits.argtypes = [i32, i32, i32, i32]
     lib.bmhrl_gemm_splits.restype = C.c_int
+    lib.bmhrl_gemm_plan.argtypes = [C.POINTER(GemmDesc), C.POINTER(i32)]
+    lib.bmhrl_gemm_plan.restype = C.c_int
+    lib.bmhrl_gemm_group_plan.argtypes = [C.POINTER(GemmDesc), i32]
+    lib.bmhrl_gemm_group_plan.restype = C.c_int
     lib.bmhrl_hip_arch.restype = C.c_char_p
     lib.bmhrl_hip_abi_version.restype = C.c_int
     lib.bmhrl_deterministic_enabled.restype = C.c_int

@@ -471,6 +471,14 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bx, const
 #pragma unroll
     for (int i = 0; i < CH_B; ++i) rb[ST][i] = *reinterpret_cast<const bf16x8*>(Bk + b_off[i] + (BT ? b_kk[i] * (int)p.ldb : b_kk[i]));
   };
+  // a k-contiguous chunk [k, k + 8) that straddles the end of the reduction: its elements at k >= K are the operand's
+  // padding columns (any value, NaN included) -- zeroed element by element, not per chunk
+  auto kmask8 = [&](bf16x8 v, const int k) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (k + j >= k_end) v[j] = (bf16_t)0.f;
+    return v;
+  };
   auto load_tail = [&](int k0, auto set_) {
     constexpr int ST = decltype(set_)::value;   // ragged last tile: clamp, then zero what lies at k >= K
 #pragma unroll
@@ -479,7 +487,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bx, const
       const bool ok = AT ? (k < k_end) : (k < K8);
       const bf16_t* q = AT ? Ag + (long)min(k, p.K - 1) * p.lda + a_off[i] : Ag + a_off[i] + min(k, Klast8);
       const bf16x8 v = *reinterpret_cast<const bf16x8*>(q);
-      ra[ST][i] = ok ? v : zero_bf16x8();
+      ra[ST][i] = ok ? (AT ? v : kmask8(v, k)) : zero_bf16x8();
     }
 #pragma unroll
     for (int i = 0; i < CH_B; ++i) {
@@ -487,7 +495,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bx, const
       const bool ok = BT ? (k < k_end) : (k < K8);
       const bf16_t* q = BT ? Bg + (long)min(k, p.K - 1) * p.ldb + b_off[i] : Bg + b_off[i] + min(k, Klast8);
       const bf16x8 v = *reinterpret_cast<const bf16x8*>(q);
-      rb[ST][i] = ok ? v : zero_bf16x8();
+      rb[ST][i] = ok ? (BT ? v : kmask8(v, k)) : zero_bf16x8();
     }
   };
   auto store_tiles = [&](int buf, auto set_) {
@@ -1109,10 +1117,19 @@ bool uses_glds(const GemmArgs& a, int a_trans, int b_trans) {
   return !no_glds && a.K % BK == 0 && a_span < (1l << 31) && b_span < (1l << 31) && a.M >= 8 && a.N >= 8;
 }
 
+// What bmhrl_gemm launches for one problem.  ONE decision on the host, from the descriptor alone (no pointer is dereferenced):
+// the launcher consumes it and bmhrl_gemm_plan reports it (the field order of include/bmhrl_hip.h's plan[8]).
+enum { LOOP_REG = 0, LOOP_GLDS = 1, LOOP_GLDS8 = 2 };
+enum { TILE_64 = 0, TILE_128 = 1, TILE_128x64 = 2 };
+enum { SPLIT_NONE = 0, SPLIT_ATOMIC = 1, SPLIT_ORDERED = 2 };
+enum { EPIPATH_FAST_BF16 = 0, EPIPATH_FAST_PD = 1, EPIPATH_GENERIC = 2 };
+struct GemmPlan { int loop, tile, stages, splits, split_form, epi_path, vec_ok, ordered_colsum; };
+
 template <int TM, int TN>
-hipError_t launch(const GemmArgs& a, int a_trans, int b_trans, int batch, int splits, hipStream_t s) {
+hipError_t launch(const GemmArgs& a, const GemmPlan& pl, int a_trans, int b_trans, int batch, hipStream_t s) {
   GemmArgs p = a;
   constexpr int BM = 64 * TM, BN = 64 * TN;
+  const int splits = pl.splits;
   p.tiles_m = (a.M + BM - 1) / BM;
   const int tiles_n = (a.N + BN - 1) / BN;
   p.tiles_mn = p.tiles_m * tiles_n;
@@ -1138,39 +1155,20 @@ hipError_t launch(const GemmArgs& a, int a_trans, int b_trans, int batch, int sp
   const int ktiles = (a.K + BK - 1) / BK;
   p.k_per_split = ((ktiles + splits - 1) / splits) * BK;
   dim3 grid(p.tiles_m * tiles_n, splits, batch), block(256);
-  const bool glds = uses_glds(a, a_trans, b_trans);
-  if (glds) {
-    // stages: 2 for the 128 x 128 tiles (two workgroups per CU cover each other's waits; four stages at one workgroup per
-    // CU measured equal or slower on every shape of the step: these sizes are bound by the ~70 GB/s a CU gets from L2 into
-    // LDS, not by exposed latency); 4 for the 64 x 64 tiles when the grid gives a CU at most two of them (16 KiB stages:
-    // a step is only 4 MFMAs per wave, the loads run three steps ahead -- 1024 x 1024 x 4096 dW 34 -> 21 us; with more
-    // workgroups per CU, or a K split, the smaller footprint of two stages wins: 3072 x 1024 x 4096 dW 42 vs 49 us)
-    static const int force_ns = getenv("BMHRL_GEMM_STAGES") ? atoi(getenv("BMHRL_GEMM_STAGES")) : 0;   // (tuning aid)
-    const long blocks = (long)p.tiles_m * tiles_n * batch;
-    // (Eight stages for the caption-side GEMMs -- 480 rows, 40 .. 128 tiles -- measured no better than four: 8.2 vs 7.3 us
-    // at 480 x 1024 x 1024; those launches sit on their fixed costs, not on the depth of the ring.)
-    int ns = TM == 1 && splits == 1 && blocks <= 448 ? 4 : 2;
-    if (force_ns) ns = TM == 1 ? (force_ns >= 4 ? 4 : 2) : 2;
-    // eight waves per 128 x 128 tile (gemm_glds8_kernel) when a CU gets at most one tile: BMHRL_GEMM_W8 = 0 (default) off, 1 on for
-    // grids of up to W8_MAX workgroups, 2 always.  Alone it is the faster kernel on exactly those shapes (4096 x 1024 x 3072 dX
-    // 45.0 -> 38.3 us, 4096 x 1024 x 1024 19.8 -> 18.8 us); inside the captured step, where the audio branch's kernels run beside
-    // these GEMMs, the step measured 5.24 ms with it against 5.02 ms without: its 512-thread workgroups with 96 KiB of LDS leave
-    // a CU no room for a workgroup of the other stream, which is worth more than the kernel's own time.  Off by default.
-    static const int w8 = getenv("BMHRL_GEMM_W8") ? atoi(getenv("BMHRL_GEMM_W8")) : 0;
-    static const long w8_max = getenv("BMHRL_GEMM_W8MAX") ? atol(getenv("BMHRL_GEMM_W8MAX")) : 256;
-    if constexpr (TM == 2 && TN == 2) {
-      if (w8 && splits == 1 && a.K >= 2 * BK && (w8 == 2 || blocks <= w8_max)) {
-        dim3 block8(512);
-        if (!a_trans && !b_trans) hipLaunchKernelGGL((gemm_glds8_kernel<false, false>), grid, block8, 0, s, p);
-        else if (!a_trans && b_trans) hipLaunchKernelGGL((gemm_glds8_kernel<false, true>), grid, block8, 0, s, p);
-        else if (a_trans && !b_trans) hipLaunchKernelGGL((gemm_glds8_kernel<true, false>), grid, block8, 0, s, p);
-        else hipLaunchKernelGGL((gemm_glds8_kernel<true, true>), grid, block8, 0, s, p);
-        return hipGetLastError();
-      }
+  if constexpr (TM == 2 && TN == 2) {
+    if (pl.loop == LOOP_GLDS8) {
+      dim3 block8(512);
+      if (!a_trans && !b_trans) hipLaunchKernelGGL((gemm_glds8_kernel<false, false>), grid, block8, 0, s, p);
+      else if (!a_trans && b_trans) hipLaunchKernelGGL((gemm_glds8_kernel<false, true>), grid, block8, 0, s, p);
+      else if (a_trans && !b_trans) hipLaunchKernelGGL((gemm_glds8_kernel<true, false>), grid, block8, 0, s, p);
+      else hipLaunchKernelGGL((gemm_glds8_kernel<true, true>), grid, block8, 0, s, p);
+      return hipGetLastError();
     }
+  }
+  if (pl.loop == LOOP_GLDS) {
 #define BMHRL_GLDS(AT_, BT_)                                                                                    \
     do {                                                                                                          \
-      if (TM == 1 && ns == 4) hipLaunchKernelGGL((gemm_glds_kernel<TM, TN, AT_, BT_, TM == 1 ? 4 : 2>), grid, block, 0, s, p); \
+      if (TM == 1 && pl.stages == 4) hipLaunchKernelGGL((gemm_glds_kernel<TM, TN, AT_, BT_, TM == 1 ? 4 : 2>), grid, block, 0, s, p); \
       else hipLaunchKernelGGL((gemm_glds_kernel<TM, TN, AT_, BT_, 2>), grid, block, 0, s, p);                   \
     } while (0)
     if (!a_trans && !b_trans) BMHRL_GLDS(false, false);
@@ -1319,6 +1317,10 @@ int prepare(const bmhrl_gemm_desc* d, GemmArgs& a, TilePlan& tp, int& batch) {
   if (d->epilogue == BMHRL_EPI_DSCORE || d->epilogue == BMHRL_EPI_RELU_BWD) BMHRL_CHECK_ARG(d->aux != nullptr);
   if (d->epilogue == BMHRL_EPI_PROB) BMHRL_CHECK_ARG(d->rowvec2 != nullptr);
   BMHRL_CHECK_ARG(d->dropout_p >= 0.f && d->dropout_p < 1.f);
+  // `accumulate` adds to the fp32 output only: with a bf16 output the vector and the scalar store paths disagreed on whether
+  // Cb receives v or C_old + v, and the column sums counted C_old under BMHRL_DETERMINISTIC (the ordered pass sums the
+  // stored output) but not without it -- neither combination has a caller, both are refused
+  BMHRL_CHECK_ARG(!d->accumulate || (!d->Cb && !d->colsum));
   a.M = d->M; a.N = d->N; a.K = d->K; a.batch2 = d->batch2;
   a.A = (const bf16_t*)d->A; a.lda = d->lda; a.a_sb1 = d->a_sb1; a.a_sb2 = d->a_sb2;
   a.B = (const bf16_t*)d->B; a.ldb = d->ldb; a.b_sb1 = d->b_sb1; a.b_sb2 = d->b_sb2;
@@ -1358,7 +1360,100 @@ int prepare(const bmhrl_gemm_desc* d, GemmArgs& a, TilePlan& tp, int& batch) {
   if (tp.splits > 1 && d->accumulate && !a.split_ws) return -22;
   return 0;
 }
+
+// prepare() + the main loop, its LDS stages and the epilogue's store path: everything bmhrl_gemm decides about a problem
+int plan_problem(const bmhrl_gemm_desc* d, GemmArgs& a, GemmPlan& pl, int& batch) {
+  TilePlan tp;
+  if (const int rc = prepare(d, a, tp, batch)) return rc;
+  const int TM = tp.mid || tp.big ? 2 : 1, TN = tp.big && !tp.mid ? 2 : 1;
+  pl.tile = tp.mid ? TILE_128x64 : tp.big ? TILE_128 : TILE_64;
+  pl.splits = tp.splits;
+  pl.loop = LOOP_REG;
+  pl.stages = 2;                                  // (the register-staged loop: two LDS buffers)
+  if (uses_glds(a, d->a_trans, d->b_trans)) {
+    // stages: 2 for the 128 x 128 tiles (two workgroups per CU cover each other's waits; four stages at one workgroup per
+    // CU measured equal or slower on every shape of the step: these sizes are bound by the ~70 GB/s a CU gets from L2 into
+    // LDS, not by exposed latency); 4 for the 64 x 64 tiles when the grid gives a CU at most two of them (16 KiB stages:
+    // a step is only 4 MFMAs per wave, the loads run three steps ahead -- 1024 x 1024 x 4096 dW 34 -> 21 us; with more
+    // workgroups per CU, or a K split, the smaller footprint of two stages wins: 3072 x 1024 x 4096 dW 42 vs 49 us)
+    static const int force_ns = getenv("BMHRL_GEMM_STAGES") ? atoi(getenv("BMHRL_GEMM_STAGES")) : 0;   // (tuning aid)
+    const long blocks = (long)((d->M + 64 * TM - 1) / (64 * TM)) * ((d->N + 64 * TN - 1) / (64 * TN)) * batch;
+    // (Eight stages for the caption-side GEMMs -- 480 rows, 40 .. 128 tiles -- measured no better than four: 8.2 vs 7.3 us
+    // at 480 x 1024 x 1024; those launches sit on their fixed costs, not on the depth of the ring.)
+    int ns = TM == 1 && tp.splits == 1 && blocks <= 448 ? 4 : 2;
+    if (force_ns) ns = TM == 1 ? (force_ns >= 4 ? 4 : 2) : 2;
+    pl.loop = LOOP_GLDS;
+    pl.stages = ns;
+    // eight waves per 128 x 128 tile (gemm_glds8_kernel) when a CU gets at most one tile: BMHRL_GEMM_W8 = 0 (default) off, 1 on for
+    // grids of up to W8_MAX workgroups, 2 always.  Alone it is the faster kernel on exactly those shapes (4096 x 1024 x 3072 dX
+    // 45.0 -> 38.3 us, 4096 x 1024 x 1024 19.8 -> 18.8 us); inside the captured step, where the audio branch's kernels run beside
+    // these GEMMs, the step measured 5.24 ms with it against 5.02 ms without: its 512-thread workgroups with 96 KiB of LDS leave
+    // a CU no room for a workgroup of the other stream, which is worth more than the kernel's own time.  Off by default.
+    static const int w8 = getenv("BMHRL_GEMM_W8") ? atoi(getenv("BMHRL_GEMM_W8")) : 0;
+    static const long w8_max = getenv("BMHRL_GEMM_W8MAX") ? atol(getenv("BMHRL_GEMM_W8MAX")) : 256;
+    if (TM == 2 && TN == 2 && w8 && tp.splits == 1 && d->K >= 2 * BK && (w8 == 2 || blocks <= w8_max)) {
+      pl.loop = LOOP_GLDS8;
+      pl.stages = 3;
+    }
+  }
+  pl.split_form = tp.splits == 1 ? SPLIT_NONE : a.split_ws ? SPLIT_ORDERED : SPLIT_ATOMIC;
+  // (a K split's partial tiles leave through the generic epilogue's split branches)
+  pl.epi_path = tp.splits == 1 && a.fast_bf16 ? EPIPATH_FAST_BF16 : tp.splits == 1 && a.fast_pd ? EPIPATH_FAST_PD : EPIPATH_GENERIC;
+  pl.vec_ok = a.vec_ok;
+  pl.ordered_colsum = bmhrl_deterministic() && a.colsum != nullptr;
+  return 0;
+}
+
+// the problems of one bmhrl_gemm_group call (n <= 4): < 0 a refused descriptor, 1 one gemm_group_kernel launch serves them all
+// (every one a 64 x 64-tile problem of the same operand layout on the register-staged loop, no second pass), 0 one by one
+int group_prepare(const bmhrl_gemm_desc* d, int n, GemmGroup& g, int& total) {
+  GemmArgs* ps[4] = {&g.p0, &g.p1, &g.p2, &g.p3};
+  bool same = n > 1;
+  total = 0;
+  for (int i = 0; i < n; ++i) {
+    GemmPlan pl;
+    int batch;
+    if (const int rc = plan_problem(d + i, *ps[i], pl, batch)) return rc;
+    GemmArgs& p = *ps[i];
+    same = same && pl.tile == TILE_64 && pl.loop == LOOP_REG && d[i].a_trans == d[0].a_trans && d[i].b_trans == d[0].b_trans &&
+           pl.split_form != SPLIT_ORDERED && !pl.ordered_colsum;      // (ordered K splits / column sums are passes of bmhrl_gemm)
+    p.tiles_m = (p.M + 63) / 64;
+    p.tiles_mn = p.tiles_m * ((p.N + 63) / 64);
+    p.splits = pl.splits;
+    p.dbg = 0;
+    const int ktiles = (p.K + BK - 1) / BK;
+    p.k_per_split = ((ktiles + pl.splits - 1) / pl.splits) * BK;
+    g.first[i] = total;
+    total += p.tiles_mn * pl.splits * batch;
+  }
+  return same ? 1 : 0;
+}
 }  // namespace
+
+extern "C" int bmhrl_gemm_plan(const bmhrl_gemm_desc* d, int32_t plan[8]) {
+  GemmArgs a;
+  GemmPlan pl;
+  int batch;
+  if (const int rc = plan_problem(d, a, pl, batch)) return rc;
+  if (plan) {
+    plan[0] = pl.loop; plan[1] = pl.tile; plan[2] = pl.stages; plan[3] = pl.splits;
+    plan[4] = pl.split_form; plan[5] = pl.epi_path; plan[6] = pl.vec_ok; plan[7] = pl.ordered_colsum;
+  }
+  return 0;
+}
+
+extern "C" int bmhrl_gemm_group_plan(const bmhrl_gemm_desc* d, int32_t n) {
+  BMHRL_CHECK_ARG(d && n >= 1);
+  int launches = 0;
+  for (int i = 0; i < n; i += 4) {
+    GemmGroup g;
+    int total;
+    const int rc = group_prepare(d + i, n - i < 4 ? n - i : 4, g, total);
+    if (rc < 0) return rc;
+    launches += rc;
+  }
+  return launches;
+}
 
 void gemm_trace_dump(const GemmArgs& a, hipStream_t stream) {
 #ifdef BMHRL_GEMM_TRACE
@@ -1378,24 +1473,23 @@ void gemm_trace_dump(const GemmArgs& a, hipStream_t stream) {
 
 extern "C" int bmhrl_gemm(const bmhrl_gemm_desc* d, bmhrl_stream_t stream) {
   GemmArgs a;
-  TilePlan tp;
+  GemmPlan pl;
   int batch;
-  if (const int rc = prepare(d, a, tp, batch)) return rc;
-  const bool ordered_colsum = bmhrl_deterministic() && a.colsum != nullptr;
+  if (const int rc = plan_problem(d, a, pl, batch)) return rc;
   GemmArgs full = a;
-  if (ordered_colsum) a.colsum = nullptr;
+  if (pl.ordered_colsum) a.colsum = nullptr;
   hipError_t e;
-  if (tp.mid) e = launch<2, 1>(a, d->a_trans, d->b_trans, batch, tp.splits, (hipStream_t)stream);
-  else if (tp.big) e = launch<2, 2>(a, d->a_trans, d->b_trans, batch, tp.splits, (hipStream_t)stream);
-  else e = launch<1, 1>(a, d->a_trans, d->b_trans, batch, tp.splits, (hipStream_t)stream);
-  if (e == hipSuccess && ordered_colsum) {
+  if (pl.tile == TILE_128x64) e = launch<2, 1>(a, pl, d->a_trans, d->b_trans, batch, (hipStream_t)stream);
+  else if (pl.tile == TILE_128) e = launch<2, 2>(a, pl, d->a_trans, d->b_trans, batch, (hipStream_t)stream);
+  else e = launch<1, 1>(a, pl, d->a_trans, d->b_trans, batch, (hipStream_t)stream);
+  if (e == hipSuccess && pl.ordered_colsum) {
     hipLaunchKernelGGL(colsum_ordered_kernel, dim3((unsigned)((full.N + 63) / 64)), dim3(1024), 0, (hipStream_t)stream, full, d->batch1);
     e = hipGetLastError();
   }
-  if (e == hipSuccess && a.split_ws) {
+  if (e == hipSuccess && pl.split_form == SPLIT_ORDERED) {
     GemmArgs r = a;
-    r.splits = tp.splits;
-    const int ktiles = (a.K + BK - 1) / BK, tiles_per_split = (ktiles + tp.splits - 1) / tp.splits;
+    r.splits = pl.splits;
+    const int ktiles = (a.K + BK - 1) / BK, tiles_per_split = (ktiles + pl.splits - 1) / pl.splits;
     const int n_live = (ktiles + tiles_per_split - 1) / tiles_per_split;
     const long total = (long)batch * a.M * a.N;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 2048)), dim3(256), 0, (hipStream_t)stream, r, batch,
@@ -1417,31 +1511,15 @@ extern "C" int bmhrl_gemm_group(const bmhrl_gemm_desc* d, int32_t n, bmhrl_strea
     return 0;
   }
   GemmGroup g;
-  GemmArgs* ps[4] = {&g.p0, &g.p1, &g.p2, &g.p3};
-  bool same = n > 1;
-  int total = 0;
-  for (int i = 0; i < n; ++i) {
-    TilePlan tp;
-    int batch;
-    if (const int rc = prepare(d + i, *ps[i], tp, batch)) return rc;
-    GemmArgs& p = *ps[i];
-    same = same && !tp.big && !tp.mid && d[i].a_trans == d[0].a_trans && d[i].b_trans == d[0].b_trans &&
-           !uses_glds(p, d[i].a_trans, d[i].b_trans) && p.split_ws == nullptr &&
-           !(bmhrl_deterministic() && p.colsum != nullptr);      // (ordered column sums are a pass of bmhrl_gemm)
-    p.tiles_m = (p.M + 63) / 64;
-    p.tiles_mn = p.tiles_m * ((p.N + 63) / 64);
-    p.splits = tp.splits;
-    p.dbg = 0;
-    const int ktiles = (p.K + BK - 1) / BK;
-    p.k_per_split = ((ktiles + tp.splits - 1) / tp.splits) * BK;
-    g.first[i] = total;
-    total += p.tiles_mn * tp.splits * batch;
-  }
+  int total;
+  const int same = group_prepare(d, n, g, total);
+  if (same < 0) return same;
   if (!same) {
     for (int i = 0; i < n; ++i)
       if (const int rc = bmhrl_gemm(d + i, stream)) return rc;
     return 0;
   }
+  GemmArgs* ps[4] = {&g.p0, &g.p1, &g.p2, &g.p3};
   for (int i = n; i < 5; ++i) g.first[i] = total;
   for (int i = n; i < 4; ++i) *ps[i] = g.p0;
   g.n = n;

@@ -43,20 +43,16 @@ def bf16_zeros(rows: int, cols: int, device) -> torch.Tensor:
     return torch.zeros(rows, pad8(cols), dtype=torch.bfloat16, device=device)
 
 
-def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda: int, ldb: int, a_trans=False, b_trans=False,
-         batch: Tuple[int, int] = (1, 1), a_strides=(0, 0), b_strides=(0, 0), a_off=0, b_off=0,
-         C_f32: Optional[torch.Tensor] = None, ldc=0, c_strides=(0, 0), c_off=0,
-         C_bf16: Optional[torch.Tensor] = None, ldcb=0, cb_strides=(0, 0), cb_off=0,
-         epilogue=EPI_LINEAR, alpha=1.0, relu=False, accumulate=False, bias=None, residual=None, ldr=0,
-         r_strides=(0, 0), mask=None, mask_sb1=0, mask_sm=0, rowvec=None, rowvec2=None, rv_strides=(0, 0),
-         aux=None, ldaux=0, aux_strides=(0, 0), aux_off=0, dropout_p=0.0, seed=0, seed_dev=None, drop_strides=(0, 0, 0), allow_split_k=False,
-         colsum: Optional[torch.Tensor] = None, colsum_off=0, colsum_sb2=0, bias_sb2=0, colsum_sb1=0, bias_sb1=0,
-         defer: Optional[list] = None, split_ws: Optional[torch.Tensor] = None) -> None:
-    """C[b] = epilogue(A[b] @ B[b]); offsets are in elements from the tensors' data pointers.
-    split_ws: fp32 workspace of >= gemm_splits(M, N, K, batch) * batch * M * N elements: a K split then runs as partial tiles +
-    an ordered second pass instead of fp32 atomics (reproducible; C needs no zeroing).
-    defer: a list -- the problem is appended to it instead of launched; gemm_flush(list) then launches up to four of them as
-    ONE kernel (bmhrl_gemm_group: leaf products nothing in between depends on)."""
+def gemm_desc(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda: int, ldb: int, a_trans=False, b_trans=False,
+              batch: Tuple[int, int] = (1, 1), a_strides=(0, 0), b_strides=(0, 0), a_off=0, b_off=0,
+              C_f32: Optional[torch.Tensor] = None, ldc=0, c_strides=(0, 0), c_off=0,
+              C_bf16: Optional[torch.Tensor] = None, ldcb=0, cb_strides=(0, 0), cb_off=0,
+              epilogue=EPI_LINEAR, alpha=1.0, relu=False, accumulate=False, bias=None, residual=None, ldr=0,
+              r_strides=(0, 0), mask=None, mask_sb1=0, mask_sm=0, rowvec=None, rowvec2=None, rv_strides=(0, 0),
+              aux=None, ldaux=0, aux_strides=(0, 0), aux_off=0, dropout_p=0.0, seed=0, seed_dev=None, drop_strides=(0, 0, 0), allow_split_k=False,
+              colsum: Optional[torch.Tensor] = None, colsum_off=0, colsum_sb2=0, bias_sb2=0, colsum_sb1=0, bias_sb1=0,
+              split_ws: Optional[torch.Tensor] = None) -> "_lib.GemmDesc":
+    """the bmhrl_gemm_desc of gemm(...) with the same arguments (defer aside); the tensors must outlive its use"""
     _need_cuda(A, B, C_f32, C_bf16)
     d = _lib.GemmDesc()
     d.M, d.N, d.K = M, N, K
@@ -77,10 +73,55 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda: int, 
     d.colsum = None if colsum is None else colsum.data_ptr() + 4 * colsum_off; d.colsum_sb2 = colsum_sb2
     d.bias_sb2 = bias_sb2; d.bias_sb1 = bias_sb1; d.colsum_sb1 = colsum_sb1
     d.split_ws = _p(split_ws); d.split_ws_elems = 0 if split_ws is None else split_ws.numel()
+    return d
+
+
+def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda: int, ldb: int, a_trans=False, b_trans=False,
+         batch: Tuple[int, int] = (1, 1), a_strides=(0, 0), b_strides=(0, 0), a_off=0, b_off=0,
+         C_f32: Optional[torch.Tensor] = None, ldc=0, c_strides=(0, 0), c_off=0,
+         C_bf16: Optional[torch.Tensor] = None, ldcb=0, cb_strides=(0, 0), cb_off=0,
+         epilogue=EPI_LINEAR, alpha=1.0, relu=False, accumulate=False, bias=None, residual=None, ldr=0,
+         r_strides=(0, 0), mask=None, mask_sb1=0, mask_sm=0, rowvec=None, rowvec2=None, rv_strides=(0, 0),
+         aux=None, ldaux=0, aux_strides=(0, 0), aux_off=0, dropout_p=0.0, seed=0, seed_dev=None, drop_strides=(0, 0, 0), allow_split_k=False,
+         colsum: Optional[torch.Tensor] = None, colsum_off=0, colsum_sb2=0, bias_sb2=0, colsum_sb1=0, bias_sb1=0,
+         defer: Optional[list] = None, split_ws: Optional[torch.Tensor] = None) -> None:
+    """C[b] = epilogue(A[b] @ B[b]); offsets are in elements from the tensors' data pointers.
+    split_ws: fp32 workspace of >= gemm_splits(M, N, K, batch) * batch * M * N elements: a K split then runs as partial tiles +
+    an ordered second pass instead of fp32 atomics (reproducible; C needs no zeroing).
+    defer: a list -- the problem is appended to it instead of launched; gemm_flush(list) then launches up to four of them as
+    ONE kernel (bmhrl_gemm_group: leaf products nothing in between depends on)."""
+    d = gemm_desc(A, B, M, N, K, lda=lda, ldb=ldb, a_trans=a_trans, b_trans=b_trans, batch=batch, a_strides=a_strides,
+                  b_strides=b_strides, a_off=a_off, b_off=b_off, C_f32=C_f32, ldc=ldc, c_strides=c_strides, c_off=c_off,
+                  C_bf16=C_bf16, ldcb=ldcb, cb_strides=cb_strides, cb_off=cb_off, epilogue=epilogue, alpha=alpha, relu=relu,
+                  accumulate=accumulate, bias=bias, residual=residual, ldr=ldr, r_strides=r_strides, mask=mask, mask_sb1=mask_sb1,
+                  mask_sm=mask_sm, rowvec=rowvec, rowvec2=rowvec2, rv_strides=rv_strides, aux=aux, ldaux=ldaux,
+                  aux_strides=aux_strides, aux_off=aux_off, dropout_p=dropout_p, seed=seed, seed_dev=seed_dev,
+                  drop_strides=drop_strides, allow_split_k=allow_split_k, colsum=colsum, colsum_off=colsum_off,
+                  colsum_sb2=colsum_sb2, bias_sb2=bias_sb2, colsum_sb1=colsum_sb1, bias_sb1=bias_sb1, split_ws=split_ws)
     if defer is not None and _GROUP_LEAVES:
         defer.append((d, (A, B, C_f32, C_bf16, bias, residual, mask, rowvec, rowvec2, aux, seed_dev, colsum)))   # (operands kept alive)
         return
     _lib.check(_lib.load().bmhrl_gemm(C.byref(d), stream()), "bmhrl_gemm")
+
+
+GEMM_PLAN_FIELDS = ("loop", "tile", "stages", "splits", "split_form", "epi_path", "vec_ok", "ordered_colsum")
+
+
+def gemm_plan(d: "_lib.GemmDesc") -> dict:
+    """what bmhrl_gemm launches for descriptor d (bmhrl_gemm_plan: the launcher's own decision, host only) as a dict of
+    GEMM_PLAN_FIELDS; raises for a descriptor bmhrl_gemm refuses"""
+    plan = (_lib.i32 * 8)()
+    _lib.check(_lib.load().bmhrl_gemm_plan(C.byref(d), plan), "bmhrl_gemm_plan")
+    return dict(zip(GEMM_PLAN_FIELDS, plan))
+
+
+def gemm_group_plan(descs) -> int:
+    """gemm_group_kernel launches bmhrl_gemm_group makes for these descriptors (0: one by one); raises on a refused one"""
+    arr = (_lib.GemmDesc * len(descs))(*descs)
+    r = int(_lib.load().bmhrl_gemm_group_plan(arr, len(descs)))
+    if r < 0:
+        _lib.check(r, "bmhrl_gemm_group_plan")
+    return r
 
 
 _GROUP_LEAVES = os.environ.get("BMHRL_GEMM_GROUP", "1") == "1"      # (A/B switch: 0 launches deferred problems at once)

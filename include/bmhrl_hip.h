@@ -50,7 +50,8 @@ typedef struct bmhrl_gemm_desc {
   int32_t epilogue;
   float alpha;
   int32_t relu;
-  int32_t accumulate;                             /* C += v instead of C = v (fp32 output only) */
+  int32_t accumulate;                             /* C += v instead of C = v (fp32 output only: refused (-22) together with
+                                                     Cb or colsum) */
   int32_t allow_split_k;                          /* C is zero-initialised: long reductions may be split (fp32 atomics) */
   const float* bias;                              /* [N] or NULL */
   const float* residual; int64_t ldr, r_sb1, r_sb2; /* fp32 [M][N] or NULL */
@@ -80,6 +81,22 @@ int bmhrl_gemm_group(const bmhrl_gemm_desc* descs, int32_t n, bmhrl_stream_t str
  * memory; > 1 = fp32 atomics into a C the caller must have zeroed.  Same decision function as the launcher's.  < 0: bad
  * arguments. */
 int bmhrl_gemm_splits(int32_t M, int32_t N, int32_t K, int32_t batch);
+/* What bmhrl_gemm would launch for *d (ABI 18): the launcher's own decision, a pure host function that dereferences no
+ * pointer (only their alignment is read).  0 and plan[] filled, or < 0 where bmhrl_gemm would refuse the descriptor.
+ *   plan[0] main loop     0 register-staged (gemm_kernel: K % 64 != 0, M < 8 or N < 8), 1 direct-to-LDS, 2 direct-to-LDS 8-wave
+ *   plan[1] tile          0 64 x 64, 1 128 x 128, 2 128 x 64
+ *   plan[2] LDS stages    2 (register-staged: its two buffers), 2 or 4 (direct-to-LDS), 3 (8-wave)
+ *   plan[3] K splits      1 = none
+ *   plan[4] split form    0 none, 1 fp32 atomics into C, 2 ordered (partial tiles in split_ws + a reduction pass)
+ *   plan[5] epilogue path 0 fast bf16, 1 fast softmax (PROB / DSCORE), 2 generic (also every K split's partial tiles)
+ *   plan[6] vec_ok        1: the generic path uses 16-byte accesses away from the right edge, 0: scalar accesses throughout
+ *   plan[7] colsum pass   1: the column sums are a second, ordered pass (BMHRL_DETERMINISTIC=1), 0: atomics or none
+ * Padding of the operands (columns K .. lda, or M / N .. lda when transposed) and gaps between batch entries may hold any
+ * value, NaN included: no element outside the operands' logical extent reaches a stored output. */
+int bmhrl_gemm_plan(const bmhrl_gemm_desc* d, int32_t plan[8]);
+/* bmhrl_gemm_group's decision for descs[0 .. n): the number of gemm_group_kernel launches it makes (per four problems: 1 when
+ * they share one launch, 0 when they run one by one), < 0 for a refused descriptor. */
+int bmhrl_gemm_group_plan(const bmhrl_gemm_desc* descs, int32_t n);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused scaled-dot-product attention forward (flash style, S x S never materialised).

@@ -11,7 +11,8 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(bmhrl_[a-z0-9_]+)\s*\(", text)))
 
 
-def test_library_builds_and_exports_every_declared_symbol():
+def test_library_builds_and_exports_every_declared_symbol_at_abi_18():
+    """(ABI 18 adds the host queries bmhrl_gemm_plan / bmhrl_gemm_group_plan: the symbol set and the version below)"""
     from bmhrl_amd import build, _lib
     build.build(verbose=False)
     lib = _lib.load()
@@ -21,10 +22,10 @@ def test_library_builds_and_exports_every_declared_symbol():
         assert hasattr(lib, s), f"{s} declared in include/bmhrl_hip.h but not exported"
     assert set(_lib.PROTOTYPES) | {"bmhrl_hip_arch", "bmhrl_hip_abi_version", "bmhrl_deterministic_enabled", "bmhrl_layernorm_bwd_workspace",
                                     "bmhrl_attention_shared128_bwd_workspace", "bmhrl_attention_max_keys", "bmhrl_gemm_splits", "bmhrl_small_attention_ok",
-                                    "bmhrl_memory_attention_ok"} == set(syms)
+                                    "bmhrl_memory_attention_ok", "bmhrl_gemm_plan", "bmhrl_gemm_group_plan"} == set(syms)
     assert lib.bmhrl_layernorm_bwd_workspace(4096, 1024) == 256 * 2 * 1024      # 4 rows per wave, 4 waves per block: 256 blocks
     assert lib.bmhrl_hip_arch() == b"gfx950"
-    assert lib.bmhrl_hip_abi_version() == 17
+    assert lib.bmhrl_hip_abi_version() == 18
     import os
     from bmhrl_amd import ops
     assert lib.bmhrl_deterministic_enabled() == int(os.environ.get("BMHRL_DETERMINISTIC", "0") not in ("", "0")) == int(ops.deterministic())
@@ -32,6 +33,8 @@ def test_library_builds_and_exports_every_declared_symbol():
     # pure host query too: the video projections' weight gradients store every element once, the caption-side ones split K
     assert lib.bmhrl_gemm_splits(1024, 1024, 4096, 1) == 1 and lib.bmhrl_gemm_splits(128, 300, 480, 1) > 1
     assert lib.bmhrl_gemm_splits(0, 4, 4, 1) < 0
+    # pure host queries: a missing descriptor is refused as bmhrl_gemm refuses it (tests/test_gemm_plan_cpu.py: the plans)
+    assert lib.bmhrl_gemm_plan(None, None) == -22 and lib.bmhrl_gemm_group_plan(None, 1) == -22
     assert lib.bmhrl_small_attention_ok(30, 30, 256) == 1 and lib.bmhrl_small_attention_ok(30, 33, 256) == 0
     assert lib.bmhrl_memory_attention_ok(30, 800, 128) == 1 and lib.bmhrl_memory_attention_ok(30, 1024, 128) == 0
 
