@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # BMHRL_HIP_LIB: load another build of the same library (kernel A/B comparisons in one run); never a different backend
 LIB_PATH = os.environ.get("BMHRL_HIP_LIB") or os.path.join(_HERE, "csrc", "libbmhrl_hip.so")
 
-i32, i64, u64, f32 = C.c_int32, C.c_int64, C.c_uint64, C.c_float
+i32, i64, u64, f32, f64 = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
 ptr = C.c_void_p
 
 
@@ -124,6 +124,8 @@ PROTOTYPES = {
     "bmhrl_adam_segments": [ptr, i32, i32, ptr, ptr, ptr, ptr, f32, f32, f32, f32, f32, i32, ptr, f32, ptr],
     "bmhrl_beam_select": [ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, i32, ptr, ptr, i32, i32, i32, i32, i32, ptr],
     "bmhrl_beam_reorder": [ptr, i32, i64, ptr, i32, i32, ptr, i32, ptr],
+    "bmhrl_rewards": [ptr, i64, ptr, i32, i64, ptr, i64, ptr, ptr, ptr, i32, i32, i32, f64, i32, i32, i32, ptr, i64, ptr, i64,
+                      ptr],
 }
 
 _lib = None

@@ -737,3 +737,36 @@ def beam_reorder(table, n_buffers, n_blocks, parent, rows, K, t, phase):
         raise ValueError("beam_reorder: table of n_buffers x 4 int64 words and an int32 parent per row expected")
     _lib.check(_lib.load().bmhrl_beam_reorder(table.data_ptr(), n_buffers, n_blocks, parent.data_ptr(), rows, K, t.data_ptr(),
                                               phase, stream()), "bmhrl_beam_reorder")
+
+
+# ---- per-prefix caption rewards (csrc/rewards.hip)
+REWARD_CIDER, REWARD_BLEU = 0, 1
+REWARDS_MAX_L, REWARDS_MAX_R = 256, 512      # BMHRL_REWARDS_MAX_L / _R of include/bmhrl_hip.h
+
+
+def rewards(hyp, vmap, eos, ref, ref_len, df_keys, df_logs, metric, n, sigma, scores, delta):
+    """per-prefix scores (B, L) fp64 and their first differences (B, L) fp32 of the sampled captions hyp (B, L) int64 against
+    ref (>= B, R) int32 word ids, ref_len (>= B) int32; see bmhrl_rewards in include/bmhrl_hip.h.  df_keys (cap, 4) int32 /
+    df_logs (cap) fp64: the CIDEr document-frequency table (None for BLEU)."""
+    _need_cuda(hyp, vmap, ref, ref_len, df_keys, df_logs, scores, delta)
+    B, L = hyp.shape
+    R = ref.shape[1]
+    if hyp.dtype != torch.int64 or vmap.dtype != torch.int32 or ref.dtype != torch.int32 or ref_len.dtype != torch.int32:
+        raise ValueError("rewards: hyp int64, vmap / ref / ref_len int32 expected")
+    if hyp.stride(1) != 1 or ref.stride(1) != 1 or not vmap.is_contiguous() or not ref_len.is_contiguous():
+        raise ValueError("rewards: hyp and ref need contiguous rows, vmap and ref_len contiguous")
+    if ref.shape[0] < B or ref_len.numel() < B:
+        raise ValueError("rewards: fewer reference rows than samples")
+    if scores.dtype != torch.float64 or delta.dtype != torch.float32 or tuple(scores.shape) != (B, L) or \
+            tuple(delta.shape) != (B, L) or scores.stride(1) != 1 or delta.stride(1) != 1:
+        raise ValueError("rewards: scores (B, L) fp64 and delta (B, L) fp32 with contiguous rows expected")
+    cap = 0
+    if df_keys is not None:
+        cap = df_keys.shape[0]
+        if df_keys.dtype != torch.int32 or tuple(df_keys.shape) != (cap, 4) or not df_keys.is_contiguous() or \
+                df_logs.dtype != torch.float64 or df_logs.numel() != cap:
+            raise ValueError("rewards: df_keys (cap, 4) int32 and df_logs (cap) fp64 expected")
+    _lib.check(_lib.load().bmhrl_rewards(hyp.data_ptr(), hyp.stride(0), vmap.data_ptr(), vmap.numel(), eos, ref.data_ptr(),
+                                         ref.stride(0), ref_len.data_ptr(), _p(df_keys), _p(df_logs), cap, metric, n,
+                                         float(sigma), B, L, R, scores.data_ptr(), scores.stride(0), delta.data_ptr(),
+                                         delta.stride(0), stream()), "bmhrl_rewards")

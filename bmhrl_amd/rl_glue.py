@@ -66,6 +66,14 @@ def segment_reward(reward: Tensor, sections: Tensor) -> Tuple[Tensor, Tensor]:
     return out, torch.nonzero(sections)
 
 
+def discount_matrix(L: int, gamma: float, n_step: int = 100, device=None) -> Tensor:
+    """(L, L) fp32 w with w[t, t + i] = gamma^i for 0 <= i < n_step: discontinue_reward without segments is x @ w.t().
+    Building it uploads gamma, so a caller inside a graph capture builds it once beforehand (rewards.py reward_fn)."""
+    d = torch.arange(L, device=device)[None, :] - torch.arange(L, device=device)[:, None]          # column - row
+    return torch.where((d >= 0) & (d < n_step), torch.as_tensor(float(gamma), device=device) ** d.clamp(min=0).float(),
+                       torch.zeros((), device=device))
+
+
 def discontinue_reward(cider_diff: Tensor, gamma: float, n_step: int = 100, segments: Optional[Tensor] = None) -> Tensor:
     """metrics/util.py discontinue_reward.  Without segments: out[b, t] = sum_{i < n_step} gamma^i x[b, t+i] as one
     (L, L) banded matrix product.  With segments: see the loop restatement for the reference's guard on the first two
@@ -74,10 +82,7 @@ def discontinue_reward(cider_diff: Tensor, gamma: float, n_step: int = 100, segm
     B, L = x.shape
     dev = x.device
     if segments is None:
-        d = torch.arange(L, device=dev)[None, :] - torch.arange(L, device=dev)[:, None]          # column - row
-        w = torch.where((d >= 0) & (d < n_step), torch.as_tensor(float(gamma), device=dev) ** d.clamp(min=0).float(),
-                        torch.zeros((), device=dev))
-        return x @ w.t()
+        return x @ discount_matrix(L, gamma, n_step, dev).t()
     sid, n_seg, in_seg = _segment_layout(segments)
     seg = segments != 0
     # rank of every segment end in the row-major list of all ends of the batch

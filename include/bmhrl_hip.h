@@ -553,6 +553,26 @@ int bmhrl_beam_select(const float* logp, int64_t ld, const float* scores_in, con
 int bmhrl_beam_reorder(const bmhrl_beam_buffer* table, int32_t n_buffers, int64_t n_blocks, const int32_t* parent,
                        int32_t rows, int32_t K, const int64_t* t, int32_t phase, bmhrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-prefix caption rewards (bmhrl_amd/rewards.py CiderScorer / BleuScorer): the score of every prefix of every sampled
+ * caption against its reference caption, as the reference's metrics/cider.py and metrics/bleu.py compute it on the host.
+ *  hyp (B, L) int64 vocab ids, row stride ldh; vmap[V]: vocab id -> word id (-1: the token yields no word; ids outside
+ *  [0, V) yield none either); eos: the vocab id of "</s>" (CIDEr stops there; -1: none); ref (B, R) int32 word ids, row
+ *  stride ldr, of which ref_len[b] (device, clamped to [0, R]) are used.  CIDEr reads the document-frequency table:
+ *  df_cap (a power of two) keys of 4 int32 word ids (-1 behind the gram; key[0] = -1: empty slot) and log(df) per key.
+ *  Writes scores (B, L) fp64 (the reference's per-prefix `rewards` row, padded as it pads) and delta (B, L) fp32
+ *  (column 0: the score, then first differences).  n: gram lengths 1..n (1 <= n <= 4); sigma: CIDEr's length penalty.
+ *  L <= BMHRL_REWARDS_MAX_L, R <= BMHRL_REWARDS_MAX_R; other shapes are refused with -22.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_REWARDS_MAX_L 256
+#define BMHRL_REWARDS_MAX_R 512
+#define BMHRL_REWARD_CIDER 0
+#define BMHRL_REWARD_BLEU 1
+int bmhrl_rewards(const int64_t* hyp, int64_t ldh, const int32_t* vmap, int32_t V, int64_t eos, const int32_t* ref,
+                  int64_t ldr, const int32_t* ref_len, const int32_t* df_keys, const double* df_logs, int32_t df_cap,
+                  int32_t metric, int32_t n, double sigma, int32_t B, int32_t L, int32_t R, double* scores, int64_t lds,
+                  float* delta, int64_t ldd, bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
