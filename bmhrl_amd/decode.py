@@ -12,8 +12,11 @@ Three forms, same tokens:
     position is a device word, so the step is captured once into a HIP graph and replayed max_len times.
 
 beam_decode / beam_decoder: beam search over the same token step on B*K rows (BeamDecoder), or over full re-runs.
+sample_decode / sample_decoder: temperature / top-k / top-p sampling, n samples per clip, over the same token step on B*n rows
+(SampleDecoder), or over full re-runs.
 """
 import math
+import random
 
 import torch
 
@@ -566,3 +569,263 @@ class BeamDecoder(IncrementalDecoder):
 
     def result(self):
         raise NotImplementedError("BeamDecoder: use run() (or beam_decode)")
+
+
+# ------------------------------------------------------------------------------------------------------------- sampling
+# Rules (both paths below implement exactly these).  Inputs: n >= 1 samples per clip, temperature T >= 0, top_k >= 0,
+# 0 < top_p <= 1, seed, length_penalty.
+#  1. clip b owns the n rows b*n .. b*n + n - 1 (sample-major, as beams); every row starts live with input start_idx and
+#     sum_logp = 0;
+#  2. at step t a live row has the model's fp32 log-probs lp (V values).  T = 0: the arg-max (the first maximum, as
+#     torch.argmax).  T > 0: q_v = exp((lp_v - max lp) / T);
+#  3. the order is lp descending, ties to the smaller token id.  top_k keeps the first k tokens of the order (k = 0 or
+#     k >= V: all); top_p keeps the shortest prefix of the order whose q-mass is >= top_p * sum q (top_p = 1: all); with
+#     both, the shorter prefix.  At least one token is kept;
+#  4. u = uniform01(seed + seed_word, ((row_offset + row) << 16) + t), the generator of csrc/common.h.  Walking the kept
+#     tokens in increasing token id and accumulating q, the pick is the first token of positive q whose inclusive sum is
+#     > u * kept_mass; if rounding leaves none, the last kept token of positive q;
+#  5. the pick's model log-prob lp_v (independent of T) is added to sum_logp and recorded with its sampling log-prob
+#     log(q_v / kept_mass) (0 for an arg-max pick) and the token (history column t + 1).  Picking end_idx finishes the row;
+#     a finished row emits pad_idx and adds nothing;
+#  6. stop after the step at which every row has finished, or after max_len steps; n_k = generated tokens up to and
+#     including the first end_idx (the steps run if none), as beam rule 5;
+#  7. the result is int64 (B, m + 1): with n = 1 the sample itself, with n > 1 per clip the row with the largest
+#     sum_logp / ((5 + n_k) / 6) ** length_penalty, ties to the lower row; pad_idx after its end; m = max n_k of the chosen.
+# T = 0, top_k = 1 and a tiny top_p each give greedy's tokens with pad_idx after each row's first end token; T = 1, k = 0,
+# p = 1 is the reference's Categorical(exp(lp)) draw (epoch_loops/captioning_bmrl_loops.py:543-583), padded after the end.
+# Rows without a finite log-prob take the arg-max (their q is undefined).
+
+_U64 = 2 ** 64
+
+
+def uniform01(seed, idx):
+    """numpy mirror of hash_u32 / uniform01 of csrc/common.h (uint64 wraparound): float64 values of the fp32 draws"""
+    import numpy as np
+    s = np.uint64(int(seed) % _U64)
+    z = np.asarray(idx, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = z * np.uint64(0x9E3779B97F4A7C15) + s
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return ((z >> np.uint64(40)).astype(np.float64)) / 16777216.0          # (hash >> 32) >> 8, times 2^-24: exact in fp32
+
+
+def _sample_args(n, temperature, top_k, top_p):
+    n, top_k = int(n), int(top_k)
+    temperature, top_p = float(temperature), float(top_p)
+    if n < 1:
+        raise ValueError(f"n must be >= 1, got {n}")
+    if not (temperature >= 0 and math.isfinite(temperature)):
+        raise ValueError(f"temperature must be finite and >= 0, got {temperature}")
+    if top_k < 0:
+        raise ValueError(f"top_k must be >= 0, got {top_k}")
+    if not 0 < top_p <= 1:
+        raise ValueError(f"top_p must lie in (0, 1], got {top_p}")
+    return n, temperature, top_k, top_p
+
+
+def _f32(x):
+    """the fp32 value the kernel sees for a host float"""
+    return torch.tensor(x, dtype=torch.float32).item()
+
+
+def sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, n=1, temperature=1.0, top_k=0,
+                  top_p=1.0, seed=None, length_penalty=0.0, return_samples=False, incremental=None):
+    """Sampled decoding with the reference decoder's arguments (rules above).  Returns tokens (B, m + 1) int64 (rule 7), then
+    -- with return_samples -- all samples (B, n, m' + 1), their sum_logp (B, n) fp32 and the per-step model / sampling
+    log-probs (B, n, m') fp32 (m': the steps of rule 6; zeros after a row's end).  seed=None draws one from `random`.
+    incremental (default: on under the conditions beam_decode takes BeamDecoder, n <= 16) decodes through SampleDecoder;
+    otherwise every step re-runs model.inference over the (B*n)-row prefix batch in float64 (any model, CPU included)."""
+    n, temperature, top_k, top_p = _sample_args(n, temperature, top_k, top_p)
+    seed = random.getrandbits(62) if seed is None else int(seed) % _U64
+    with torch.no_grad():
+        device = feature_stacks['audio'].device
+        if incremental is None:
+            incremental = SampleDecoder.enabled
+        found = None
+        if (incremental and hasattr(model, "encode_memory") and not model.training and device.type == "cuda"
+                and modality == "audio_video" and max_len >= 1 and n <= ops.BEAM_MAX
+                and 1 <= getattr(model, "voc_size", 0) <= ops.SAMPLE_MAX_V):
+            dec = SampleDecoder.for_batch(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, n)
+            dec.set_params(temperature, top_k, top_p)
+            if dec.begin(feature_stacks):
+                found = dec.run(seed)
+        if found is None:
+            found = _sample_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, n, temperature, top_k,
+                                  top_p, seed)
+        return _sample_result(*found, end_idx, length_penalty, return_samples)
+
+
+def sample_decoder(n=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, length_penalty=0.0):
+    """a decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality), e.g.
+    validation_1by1_loop(cfg, model, loader, sample_decoder(4, top_p=0.9), epoch, TBoard); seed=None: a fresh seed per call"""
+    n, temperature, top_k, top_p = _sample_args(n, temperature, top_k, top_p)
+
+    def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
+        return sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, n=n,
+                             temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, length_penalty=length_penalty)
+    return decoder
+
+
+def _sample_choose(lp, temperature, top_k, top_p, u):
+    """rules 2-4 in float64 for every row of lp (R, V) with draws u (R,) -> (picks (R,) int64, sampling log-probs (R,))"""
+    R, V = lp.shape
+    lp = torch.nan_to_num(lp.double(), nan=float("-inf"), posinf=float("inf"))
+    arg = lp.argmax(1)
+    zero = torch.zeros(R, dtype=torch.float64, device=lp.device)
+    T, p = _f32(temperature), _f32(top_p)
+    if T == 0 or top_k == 1:
+        return arg, zero
+    M = lp.max(1, keepdim=True).values
+    dead = ~torch.isfinite(M.squeeze(1))
+    finite = torch.isfinite(lp)
+    q = torch.where(finite, torch.exp((lp - M) / T), torch.zeros_like(lp))
+    kept = torch.ones_like(finite)
+    if 0 < top_k < V or p < 1:
+        order = torch.sort(-lp, dim=1, stable=True).indices
+        cum = q.gather(1, order).cumsum(1)
+        c = torch.full((R,), V, dtype=torch.long, device=lp.device)
+        if 0 < top_k < V:
+            c.clamp_(max=top_k)
+        if p < 1:
+            c = torch.minimum(c, ((cum < p * cum[:, -1:]).sum(1) + 1).clamp(max=V))
+        kept = torch.zeros_like(finite).scatter(1, order, torch.arange(V, device=lp.device).unsqueeze(0) < c.unsqueeze(1))
+    incl = torch.where(kept, q, torch.zeros_like(q)).cumsum(1)
+    mass = incl[:, -1]
+    cand = kept & (q > 0)
+    hit = cand & (incl > (u.double() * mass).unsqueeze(1))
+    last = V - 1 - cand.flip(1).to(torch.uint8).argmax(1)
+    pick = torch.where(hit.any(1), hit.to(torch.uint8).argmax(1), last)
+    logq = (lp.gather(1, pick.unsqueeze(1)).squeeze(1) - M.squeeze(1)) / T - torch.log(mass)
+    return torch.where(dead, arg, pick), torch.where(dead, zero, logq)
+
+
+def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, temperature, top_k, top_p, seed):
+    """rules 1-6 over full re-runs of model.inference on the (B*n)-row prefix batch -> (tokens (B, n, steps + 1),
+    sum_logp (B, n), step logp (B, n, steps), step logq (B, n, steps), steps)"""
+    import numpy as np
+    B = fs['audio'].shape[0]
+    dev = fs['audio'].device
+    R = B * n
+    rep = {k: v.repeat_interleave(n, 0) if torch.is_tensor(v) and v.dim() and v.shape[0] == B else v for k, v in fs.items()}
+    x = ((rep['rgb'], rep['flow']), rep['audio'])
+    fin = torch.zeros(R, dtype=torch.bool, device=dev)
+    hist = torch.full((R, 1), start_idx, dtype=torch.long, device=dev)
+    sum_logp = torch.zeros(R, dtype=torch.float64, device=dev)
+    slp, slq = [], []
+    rows = np.arange(R, dtype=np.uint64) << np.uint64(16)
+    steps = 0
+    while steps < max_len:
+        lp = model.inference(x, hist, make_masks(rep, hist, modality, pad_idx))[:, -1].double()
+        u = torch.from_numpy(uniform01(seed, rows + np.uint64(steps))).to(dev)
+        pick, logq = _sample_choose(lp, temperature, top_k, top_p, u)
+        g = lp.gather(1, pick.unsqueeze(1)).squeeze(1)
+        pick = torch.where(fin, torch.full_like(pick, pad_idx), pick)
+        g, logq = torch.where(fin, torch.zeros_like(g), g), torch.where(fin, torch.zeros_like(logq), logq)
+        sum_logp += g
+        slp.append(g)
+        slq.append(logq)
+        hist = torch.cat([hist, pick.unsqueeze(1)], 1)
+        fin |= pick == end_idx
+        steps += 1
+        if bool(fin.all()):
+            break
+    f32 = lambda a: a.float().view(B, n, -1)
+    return (hist.view(B, n, -1), sum_logp.float().view(B, n), f32(torch.stack(slp, 1)), f32(torch.stack(slq, 1)), steps)
+
+
+def _sample_result(toks, sum_logp, step_logp, step_logq, steps, end_idx, length_penalty, return_samples):
+    """rules 6-7 over (B, n, >= steps + 1) samples"""
+    B, n = sum_logp.shape
+    toks = toks[..., :steps + 1]
+    is_end = toks[..., 1:] == end_idx
+    before = (is_end.cumsum(-1) == 0).sum(-1)
+    n_k = torch.where(is_end.any(-1), before + 1, torch.full_like(before, steps))
+    final = sum_logp / ((5.0 + n_k.to(sum_logp.dtype)) / 6.0) ** length_penalty
+    best = torch.sort(-final, dim=1, stable=True).indices[:, 0]
+    rows = torch.arange(B, device=sum_logp.device)
+    m = int(n_k[rows, best].max()) if B else 0
+    out = toks[rows, best, :m + 1].clone()
+    if not return_samples:
+        return out
+    return out, toks.clone(), sum_logp.clone(), step_logp[..., :steps].clone(), step_logq[..., :steps].clone()
+
+
+class SampleDecoder(IncrementalDecoder):
+    """IncrementalDecoder's token step on B*n rows (sample-major; the per-clip memory K|V is shared, its attentions take a
+    clip's n rows as n queries, as BeamDecoder's), followed by one bmhrl_sample_step launch inside the same captured graph
+    (csrc/sample.hip: rules 2-5 for every row).  Rows never change parents, so nothing is reordered.  The draw's seed is a
+    device word written before every decode: a cached graph draws fresh samples for a new seed and repeats them for the
+    same seed.  temperature / top_k / top_p are launch arguments: set_params() captures the step again when they change."""
+
+    _cache_attr = "_sample_decoders"
+
+    @classmethod
+    def for_batch(cls, agent, fs, max_len, start_idx, end_idx, pad_idx, n=1):
+        B, Tv = fs['rgb'].shape[:2]
+        Ta = fs['audio'].shape[1]
+        key = (B, -(-Tv // 64) * 64, -(-Ta // 64) * 64, int(max_len), int(start_idx), int(end_idx), int(pad_idx), int(n),
+               fs['rgb'].device)
+        cache = agent.__dict__.setdefault(cls._cache_attr, {})
+        dec = cache.get(key)
+        if dec is None:
+            if len(cache) >= 8:
+                cache.pop(next(iter(cache)))
+            dec = cache[key] = cls(agent, *key[:7], device=key[8], beams=key[7])
+        return dec
+
+    def __init__(self, agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device, beams=1, temperature=1.0,
+                 top_k=0, top_p=1.0):
+        if not 1 <= beams <= ops.BEAM_MAX:
+            raise ValueError(f"SampleDecoder: {beams} samples per clip outside [1, 16]")
+        if not 1 <= agent.voc_size <= ops.SAMPLE_MAX_V:
+            raise ValueError(f"SampleDecoder: vocabulary of {agent.voc_size} outside [1, {ops.SAMPLE_MAX_V}]")
+        self.params = _sample_args(beams, temperature, top_k, top_p)[1:]
+        super().__init__(agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device, beams=beams)
+
+    def set_params(self, temperature, top_k, top_p):
+        params = _sample_args(self.K, temperature, top_k, top_p)[1:]
+        if params != self.params:
+            self.params = params
+            if self.graph is not None:
+                self._capture()
+
+    def _init_search(self):
+        R, dev, L = self.R, self.dev, self.max_len + 1
+        self.sum_logp = torch.zeros(R, device=dev)
+        self.step_logp = torch.zeros(R, L, device=dev)          # column t: step t (same row stride as `out`)
+        self.step_logq = torch.zeros(R, L, device=dev)
+        self.seed_word = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def _reset(self):
+        super()._reset()
+        self.sum_logp.zero_()
+        self.step_logp.zero_()
+        self.step_logq.zero_()
+
+    def _choose(self, logp):
+        V = self.logp.shape[-1]
+        T, k, p = self.params
+        ops.sample_step(self.logp, V, self.R, V, T, k, p, 0, self.seed_word, self.t, self.end_idx, self.pad_idx, self.done,
+                        self.tok, self.out, self.sum_logp, self.step_logp, self.step_logq)
+
+    def run(self, seed=0):
+        """-> (tokens (B, n, m + 1), sum_logp (B, n), step logp (B, n, m), step logq (B, n, m), m): the samples after the
+        step at which every row had finished"""
+        s = int(seed) % _U64
+        self.seed_word.fill_(s - _U64 if s >= 2 ** 63 else s)
+        for i in range(self.max_len):
+            self.step()
+            if (i + 1) % self.check_every == 0 and i + 1 < self.max_len and bool(self.done.all()):
+                break
+        m = self.steps_run
+        is_end = self.out[:, 1:m + 1] == self.end_idx
+        if m and bool(is_end.any(1).all()):
+            m = int(is_end.to(torch.uint8).argmax(1).max()) + 1
+        B, n = self.B, self.K
+        return (self.out[:, :m + 1].reshape(B, n, m + 1).clone(), self.sum_logp.view(B, n).clone(),
+                self.step_logp[:, :m].reshape(B, n, m).clone(), self.step_logq[:, :m].reshape(B, n, m).clone(), m)
+
+    def result(self):
+        raise NotImplementedError("SampleDecoder: use run() (or sample_decode)")

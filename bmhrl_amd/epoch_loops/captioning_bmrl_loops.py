@@ -13,7 +13,7 @@ import random
 
 import torch
 
-from ..decode import beam_decoder, greedy_decode  # noqa: F401  (beam_decoder: a decoder for the validation loops)
+from ..decode import beam_decoder, greedy_decode, sample_decoder  # noqa: F401  (beam / sample decoders for the validation loops)
 from ..model.masking import make_masks
 
 

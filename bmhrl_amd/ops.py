@@ -3,6 +3,7 @@ every call is enqueued on torch's current HIP stream.  No wrapper has a CPU path
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Tuple
 
@@ -770,3 +771,38 @@ def rewards(hyp, vmap, eos, ref, ref_len, df_keys, df_logs, metric, n, sigma, sc
                                          ref.stride(0), ref_len.data_ptr(), _p(df_keys), _p(df_logs), cap, metric, n,
                                          float(sigma), B, L, R, scores.data_ptr(), scores.stride(0), delta.data_ptr(),
                                          delta.stride(0), stream()), "bmhrl_rewards")
+
+
+# ---- sampled caption decoding (csrc/sample.hip)
+SAMPLE_MAX_V = 16384                          # BMHRL_SAMPLE_MAX_V of include/bmhrl_hip.h
+
+
+def sample_step(logp, ld, rows, V, temperature, top_k, top_p, seed, seed_dev, t, end_idx, pad_idx, finished, tok, out,
+                sum_logp, step_logp=None, step_logq=None, row_offset=0):
+    """one step of the sampling rules for every row (see bmhrl_sample_step in include/bmhrl_hip.h): logp (rows, ld >= V)
+    fp32; finished (rows) uint8 / bool, tok (rows) int64, sum_logp (rows) fp32 updated in place; out (rows, cols) int64 gets
+    column t + 1, step_logp / step_logq (rows, cols) fp32 (optional, the same row stride) column t.  seed_dev: None or a
+    (1,) int64 word added to seed (uint64 wraparound); t: (1,) int64 device word."""
+    _need_cuda(logp, seed_dev, t, finished, tok, out, sum_logp, step_logp, step_logq)
+    if not (1 <= V <= SAMPLE_MAX_V and ld >= V and rows >= 1 and logp.dtype == torch.float32
+            and logp.numel() >= (rows - 1) * ld + V):
+        raise ValueError(f"sample_step: need 1 <= V <= {SAMPLE_MAX_V} and fp32 logp rows (rows, ld >= V)")
+    if not (math.isfinite(temperature) and temperature >= 0 and top_k >= 0 and 0 < top_p <= 1):
+        raise ValueError("sample_step: need a finite temperature >= 0, top_k >= 0 and 0 < top_p <= 1")
+    if not (0 <= pad_idx < V and row_offset >= 0 and 0 <= seed < 2**64):
+        raise ValueError("sample_step: need 0 <= pad_idx < V, row_offset >= 0 and a uint64 seed")
+    for x, dts in ((finished, (torch.uint8, torch.bool)), (tok, (torch.int64,)), (sum_logp, (torch.float32,))):
+        if x.dtype not in dts or x.numel() < rows or not x.is_contiguous():
+            raise ValueError(f"sample_step: expected a contiguous {dts[0]} buffer of {rows} elements")
+    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != rows or out.stride(1) != 1:
+        raise ValueError("sample_step: out must be (rows, cols) int64 with contiguous rows")
+    for h in (step_logp, step_logq):
+        if h is not None and (h.dtype != torch.float32 or h.shape != out.shape or h.stride() != out.stride()):
+            raise ValueError("sample_step: step_logp / step_logq must be fp32 with the shape and strides of out")
+    if t.dtype != torch.int64 or (seed_dev is not None and seed_dev.dtype != torch.int64):
+        raise ValueError("sample_step: t and seed_dev are int64 words")
+    _lib.check(_lib.load().bmhrl_sample_step(logp.data_ptr(), ld, rows, V, float(temperature), int(top_k), float(top_p),
+                                             int(seed), _p(seed_dev), t.data_ptr(), row_offset, end_idx, pad_idx,
+                                             finished.data_ptr(), tok.data_ptr(), out.data_ptr(), out.stride(0),
+                                             sum_logp.data_ptr(), _p(step_logp), _p(step_logq), stream()),
+               "bmhrl_sample_step")

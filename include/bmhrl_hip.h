@@ -573,6 +573,26 @@ int bmhrl_rewards(const int64_t* hyp, int64_t ldh, const int32_t* vmap, int32_t 
                   int32_t metric, int32_t n, double sigma, int32_t B, int32_t L, int32_t R, double* scores, int64_t lds,
                   float* delta, int64_t ldd, bmhrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sampled caption decoding (bmhrl_amd/decode.py SampleDecoder; the rules are at the top of its sampling section).  One step
+ * for every row r of logp (rows, ld) fp32 log-probs, t read from the device word t[0]:
+ *  finished[r] != 0: tok[r] = pad_idx, out[r][t + 1] = pad_idx, step_logp / step_logq [r][t] = 0, sum_logp unchanged;
+ *  otherwise q_v = exp((lp_v - max lp) / temperature) over the order (lp descending, ties to the smaller id); top_k (0 or
+ *  >= V: all) and top_p (1: all) keep the shorter prefix of that order (count k; mass >= top_p * sum q), at least one token;
+ *  u = uniform01(seed + seed_dev[0], ((row_offset + r) << 16) + t) (common.h; seed_dev may be null: 0); the pick is the
+ *  first kept token of positive q, in token-id order, whose inclusive q sum exceeds u * kept mass (none: the last such
+ *  token).  temperature = 0, top_k = 1 and rows without a finite entry take the arg-max (first maximum; step_logq 0).
+ *  Writes tok[r], out[r][t + 1], sum_logp[r] += lp_pick, finished[r] = 1 when the pick is end_idx, step_logp[r][t] =
+ *  lp_pick and step_logq[r][t] = log(q_pick / kept mass) (both optional, row stride ld_out like out); the history
+ *  entries only when t + 1 < ld_out.  1 <= V <= BMHRL_SAMPLE_MAX_V, temperature finite >= 0, top_k >= 0,
+ *  0 < top_p <= 1, 0 <= pad_idx < V; other arguments are refused with -22.  Deterministic: no atomics.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_SAMPLE_MAX_V 16384
+int bmhrl_sample_step(const float* logp, int64_t ld, int32_t rows, int32_t V, float temperature, int32_t top_k, float top_p,
+                      uint64_t seed, const uint64_t* seed_dev, const int64_t* t, int64_t row_offset, int32_t end_idx,
+                      int32_t pad_idx, uint8_t* finished, int64_t* tok, int64_t* out, int64_t ld_out, float* sum_logp,
+                      float* step_logp, float* step_logq, bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
