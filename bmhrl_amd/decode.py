@@ -37,31 +37,56 @@ def greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, m
         B = feature_stacks['audio'].shape[0]
         device = feature_stacks['audio'].device
         memoise = memoise and hasattr(model, "encode_memory") and not model.training
-        if incremental is None:
-            incremental = IncrementalDecoder.enabled
-        if incremental and memoise and device.type == "cuda" and modality == "audio_video" and max_len >= 1:
-            dec = IncrementalDecoder.for_batch(model, feature_stacks, max_len, start_idx, end_idx, pad_idx)
-            if dec.begin(feature_stacks):
-                return dec.run(return_first)
+        dec = _incremental(IncrementalDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx,
+                           incremental=incremental if memoise else False)
+        if dec is not None:
+            return dec.run(return_first)
         done = torch.zeros(B, 1, dtype=torch.bool, device=device)
         trg = torch.full((B, 1), start_idx, dtype=torch.long, device=device)
         first = None
-        x = ((feature_stacks['rgb'], feature_stacks['flow']), feature_stacks['audio'])
+        rep, x = _rerun_setup(feature_stacks, 1)
         memory, kv_cache = None, {}
         while trg.size(-1) <= max_len and not bool(done.all()):
-            masks = make_masks(feature_stacks, trg, modality, pad_idx)
             if memoise:
+                masks = make_masks(feature_stacks, trg, modality, pad_idx)
                 if memory is None:
                     memory = model.encode_memory(x, masks)
-                preds = model.inference_from_memory(memory, trg, masks, kv_cache)
+                last = model.inference_from_memory(memory, trg, masks, kv_cache)[:, -1]
             else:
-                preds = model.inference(x, trg, masks)
+                last = _rerun_logp(model, x, rep, trg, modality, pad_idx)
             if first is None:
-                first = preds[:, -1].clone()
-            nxt = preds[:, -1].argmax(dim=-1, keepdim=True)
+                first = last.clone()
+            nxt = last.argmax(dim=-1, keepdim=True)
             trg = torch.cat([trg, nxt], dim=-1)
             done = done | (nxt == end_idx)
     return (trg, first) if return_first else trg
+
+
+def _incremental(cls, model, fs, modality, max_len, start_idx, end_idx, pad_idx, rows=1, incremental=None, params=None):
+    """the decoder of class `cls` (`rows` rows per clip) with the clip batch begun, or None: take the re-run path.
+    incremental=None: the class's `enabled`; params: SampleDecoder.set_params arguments, set before begin()"""
+    if incremental is None:
+        incremental = cls.enabled
+    if not (incremental and hasattr(model, "encode_memory") and not model.training and fs['audio'].device.type == "cuda"
+            and modality == "audio_video" and max_len >= 1 and cls._fits(model, rows)):
+        return None
+    dec = cls.for_batch(model, fs, max_len, start_idx, end_idx, pad_idx, rows)
+    if params is not None:
+        dec.set_params(*params)
+    return dec if dec.begin(fs) else None
+
+
+def _rerun_setup(fs, rows):
+    """(the feature dict with every clip's tensors repeated `rows` times, sample-major; the agent's input x of it)"""
+    B = fs['audio'].shape[0]
+    rep = fs if rows == 1 else {k: v.repeat_interleave(rows, 0) if torch.is_tensor(v) and v.dim() and v.shape[0] == B else v
+                                for k, v in fs.items()}
+    return rep, ((rep['rgb'], rep['flow']), rep['audio'])
+
+
+def _rerun_logp(model, x, rep, hist, modality, pad_idx):
+    """fp32 log-probs (rows, V) of the token after the prefixes `hist`: a full re-run of model.inference"""
+    return model.inference(x, hist, make_masks(rep, hist, modality, pad_idx))[:, -1].float()
 
 
 def bimodal_decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
@@ -97,17 +122,24 @@ class IncrementalDecoder:
     _cache_attr = "_incremental_decoders"
 
     @classmethod
-    def for_batch(cls, agent, fs, max_len, start_idx, end_idx, pad_idx):
+    def for_batch(cls, agent, fs, max_len, start_idx, end_idx, pad_idx, rows=1):
+        """the class's cached decoder for a clip batch of these shapes; rows: rows per clip (beams, samples)"""
         B, Tv = fs['rgb'].shape[:2]
         Ta = fs['audio'].shape[1]
-        key = (B, -(-Tv // 64) * 64, -(-Ta // 64) * 64, int(max_len), int(start_idx), int(end_idx), int(pad_idx), fs['rgb'].device)
+        key = (B, -(-Tv // 64) * 64, -(-Ta // 64) * 64, int(max_len), int(start_idx), int(end_idx), int(pad_idx), int(rows),
+               fs['rgb'].device)
         cache = agent.__dict__.setdefault(cls._cache_attr, {})
         dec = cache.get(key)
         if dec is None:
             if len(cache) >= 8:                         # shapes of a validation set fall into a few capacity buckets
                 cache.pop(next(iter(cache)))
-            dec = cache[key] = cls(agent, *key[:7], device=key[7])
+            dec = cache[key] = cls(agent, *key[:7], device=key[8], beams=key[7])
         return dec
+
+    @classmethod
+    def _fits(cls, model, rows):
+        """the class's own limit on top of the conditions of _incremental"""
+        return rows == 1
 
     def __init__(self, agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device, beams=1):
         self.agent = agent
@@ -210,15 +242,20 @@ class IncrementalDecoder:
         return True
 
     def run(self, return_first=False):
+        """steps until max_len or, looked at every check_every tokens, until everything has finished -> result()"""
         first = None
         for i in range(self.max_len):
             self.step()
             if i == 0 and return_first:
                 first = self.logp[:, 0].clone()
-            if (i + 1) % self.check_every == 0 and i + 1 < self.max_len and bool(self.done.all()):
+            if (i + 1) % self.check_every == 0 and i + 1 < self.max_len and self._all_done(i):
                 break
         trg = self.result()
         return (trg, first) if return_first else trg
+
+    def _all_done(self, i):
+        """has every row finished after step i? (one host read)"""
+        return bool(self.done.all())
 
     def step(self):
         if self.graph is not None:
@@ -227,14 +264,17 @@ class IncrementalDecoder:
             self._token_step()
         self.steps_run += 1
 
-    def result(self):
-        """tokens up to the step at which every sample had produced </s> (the reference's loop condition, :61-76)"""
+    def _steps_to_end(self):
+        """the step at which every row had produced </s> (the reference's loop condition, :61-76), else the steps run"""
         n = self.steps_run
-        out = self.out[:, :n + 1]
-        is_end = out[:, 1:] == self.end_idx
+        is_end = self.out[:, 1:n + 1] == self.end_idx
         if n and bool(is_end.any(1).all()):
-            n = int(is_end.float().argmax(1).max()) + 1
-        return out[:, :n + 1].clone()
+            n = int(is_end.to(torch.uint8).argmax(1).max()) + 1
+        return n
+
+    def result(self):
+        """tokens up to the step at which every sample had produced </s>"""
+        return self.out[:, :self._steps_to_end() + 1].clone()
 
     # ------------------------------------------------------------------ graph
     def _weights(self):
@@ -402,17 +442,9 @@ def beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, mod
     if K < 1:
         raise ValueError(f"beam_size must be >= 1, got {beam_size}")
     with torch.no_grad():
-        device = feature_stacks['audio'].device
-        if incremental is None:
-            incremental = BeamDecoder.enabled
-        found = None
-        if (incremental and hasattr(model, "encode_memory") and not model.training and device.type == "cuda"
-                and modality == "audio_video" and max_len >= 1 and K <= min(ops.BEAM_MAX, getattr(model, "voc_size", 0))):
-            dec = BeamDecoder.for_batch(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, K)
-            if dec.begin(feature_stacks):
-                found = dec.run()
-        if found is None:
-            found = _beam_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, K)
+        dec = _incremental(BeamDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, K, incremental)
+        found = dec.run() if dec is not None else _beam_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
+                                                              modality, K)
         return _beam_result(*found, end_idx, length_penalty, return_scores, return_beams)
 
 
@@ -432,8 +464,7 @@ def _beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K):
     """rules 1-4 over full re-runs of model.inference on the prefix batch -> (tokens (B, K, n + 1), scores (B, K), n)"""
     B = fs['audio'].shape[0]
     dev = fs['audio'].device
-    rep = {k: v.repeat_interleave(K, 0) if torch.is_tensor(v) and v.dim() and v.shape[0] == B else v for k, v in fs.items()}
-    x = ((rep['rgb'], rep['flow']), rep['audio'])
+    rep, x = _rerun_setup(fs, K)
     scores = torch.full((B, K), float("-inf"), device=dev)
     scores[:, 0] = 0.0
     finished = torch.ones(B, K, dtype=torch.bool, device=dev)
@@ -441,7 +472,7 @@ def _beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K):
     hist = torch.full((B * K, 1), start_idx, dtype=torch.long, device=dev)
     steps = 0
     while steps < max_len:
-        lp = model.inference(x, hist, make_masks(rep, hist, modality, pad_idx))[:, -1].float()
+        lp = _rerun_logp(model, x, rep, hist, modality, pad_idx)
         V = lp.shape[-1]
         cand = scores.unsqueeze(-1) + lp.view(B, K, V)
         only = torch.zeros_like(cand)
@@ -471,23 +502,29 @@ def _stable_top(cand, finished, pad_idx):
     return by_score.gather(1, by_kind)[:, :K]
 
 
-def _beam_result(toks, scores, steps, end_idx, length_penalty, return_scores, return_beams):
-    """rules 5-6 over (B, K, >= steps + 1) hypotheses and their raw scores"""
-    B, K = scores.shape
-    toks = toks[..., :steps + 1]
-    is_end = toks[..., 1:] == end_idx
+def _best_hypothesis(toks, scores, steps, end_idx, length_penalty):
+    """beam rules 5-6 (sampling rules 6-7) over (B, K, >= steps + 1) hypotheses and their raw scores -> (n_k (B, K), the
+    hypotheses' order (B, K) best first, the best ones' tokens (B, n + 1))"""
+    B = scores.shape[0]
+    is_end = toks[..., 1:steps + 1] == end_idx
     before = (is_end.cumsum(-1) == 0).sum(-1)
     n_k = torch.where(is_end.any(-1), before + 1, torch.full_like(before, steps))
     final = scores / ((5.0 + n_k.to(scores.dtype)) / 6.0) ** length_penalty
     order = torch.sort(-final, dim=1, stable=True).indices
     rows = torch.arange(B, device=scores.device)
-    best = order[:, 0]
-    n = int(n_k[rows, best].max()) if B else 0
-    out = [toks[rows, best, :n + 1].clone()]
+    n = int(n_k[rows, order[:, 0]].max()) if B else 0
+    return n_k, order, toks[rows, order[:, 0], :n + 1].clone()
+
+
+def _beam_result(toks, scores, steps, end_idx, length_penalty, return_scores, return_beams):
+    """rules 5-6 over (B, K, >= steps + 1) hypotheses and their raw scores"""
+    toks = toks[..., :steps + 1]
+    n_k, order, best = _best_hypothesis(toks, scores, steps, end_idx, length_penalty)
+    out = [best]
     if return_scores:
-        out.append(scores[rows, best].clone())
+        out.append(scores.gather(1, order[:, :1]).squeeze(1))
     if return_beams:
-        m = int(n_k.max()) if B else 0
+        m = int(n_k.max()) if scores.shape[0] else 0
         out += [toks.gather(1, order.unsqueeze(-1).expand(-1, -1, toks.shape[-1]))[..., :m + 1].clone(), scores.gather(1, order)]
     return out[0] if len(out) == 1 else tuple(out)
 
@@ -507,18 +544,8 @@ class BeamDecoder(IncrementalDecoder):
     _cache_attr = "_beam_decoders"
 
     @classmethod
-    def for_batch(cls, agent, fs, max_len, start_idx, end_idx, pad_idx, beam_size=4):
-        B, Tv = fs['rgb'].shape[:2]
-        Ta = fs['audio'].shape[1]
-        key = (B, -(-Tv // 64) * 64, -(-Ta // 64) * 64, int(max_len), int(start_idx), int(end_idx), int(pad_idx),
-               int(beam_size), fs['rgb'].device)
-        cache = agent.__dict__.setdefault(cls._cache_attr, {})
-        dec = cache.get(key)
-        if dec is None:
-            if len(cache) >= 8:
-                cache.pop(next(iter(cache)))
-            dec = cache[key] = cls(agent, *key[:7], device=key[8], beams=key[7])
-        return dec
+    def _fits(cls, model, rows):
+        return rows <= min(ops.BEAM_MAX, getattr(model, "voc_size", 0))
 
     def __init__(self, agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device, beams=4):
         if not 1 <= beams <= min(ops.BEAM_MAX, agent.voc_size):
@@ -555,20 +582,17 @@ class BeamDecoder(IncrementalDecoder):
         for phase in (0, 1):
             ops.beam_reorder(self._table, self._n_buffers, self._n_blocks, self.parent, self.R, self.K, self.t, phase)
 
-    def run(self):
-        """-> (tokens (B, K, n + 1), raw scores (B, K), n): the beams after the step at which every beam had finished"""
-        for i in range(self.max_len):
-            self.step()
-            if (i + 1) % self.check_every == 0 and i + 1 < self.max_len and int(self.last_live) < i + 1:
-                break
+    def _all_done(self, i):
+        return int(self.last_live) < i + 1
+
+    def result(self):
+        """(what run() returns) -> (tokens (B, K, n + 1), raw scores (B, K), n): the beams after the step at which every
+        beam had finished"""
         n = self.steps_run
         last = int(self.last_live)
         if last < n:
             n = last + 1
         return self.out[:, :n + 1].view(self.B, self.K, n + 1).clone(), self.scores.view(self.B, self.K).clone(), n
-
-    def result(self):
-        raise NotImplementedError("BeamDecoder: use run() (or beam_decode)")
 
 
 # ------------------------------------------------------------------------------------------------------------- sampling
@@ -640,20 +664,10 @@ def sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, m
     n, temperature, top_k, top_p = _sample_args(n, temperature, top_k, top_p)
     seed = random.getrandbits(62) if seed is None else int(seed) % _U64
     with torch.no_grad():
-        device = feature_stacks['audio'].device
-        if incremental is None:
-            incremental = SampleDecoder.enabled
-        found = None
-        if (incremental and hasattr(model, "encode_memory") and not model.training and device.type == "cuda"
-                and modality == "audio_video" and max_len >= 1 and n <= ops.BEAM_MAX
-                and 1 <= getattr(model, "voc_size", 0) <= ops.SAMPLE_MAX_V):
-            dec = SampleDecoder.for_batch(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, n)
-            dec.set_params(temperature, top_k, top_p)
-            if dec.begin(feature_stacks):
-                found = dec.run(seed)
-        if found is None:
-            found = _sample_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, n, temperature, top_k,
-                                  top_p, seed)
+        dec = _incremental(SampleDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, n, incremental,
+                           params=(temperature, top_k, top_p))
+        found = dec.run(seed) if dec is not None else _sample_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
+                                                                    modality, n, temperature, top_k, top_p, seed)
         return _sample_result(*found, end_idx, length_penalty, return_samples)
 
 
@@ -708,8 +722,7 @@ def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, 
     B = fs['audio'].shape[0]
     dev = fs['audio'].device
     R = B * n
-    rep = {k: v.repeat_interleave(n, 0) if torch.is_tensor(v) and v.dim() and v.shape[0] == B else v for k, v in fs.items()}
-    x = ((rep['rgb'], rep['flow']), rep['audio'])
+    rep, x = _rerun_setup(fs, n)
     fin = torch.zeros(R, dtype=torch.bool, device=dev)
     hist = torch.full((R, 1), start_idx, dtype=torch.long, device=dev)
     sum_logp = torch.zeros(R, dtype=torch.float64, device=dev)
@@ -717,7 +730,7 @@ def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, 
     rows = np.arange(R, dtype=np.uint64) << np.uint64(16)
     steps = 0
     while steps < max_len:
-        lp = model.inference(x, hist, make_masks(rep, hist, modality, pad_idx))[:, -1].double()
+        lp = _rerun_logp(model, x, rep, hist, modality, pad_idx).double()
         u = torch.from_numpy(uniform01(seed, rows + np.uint64(steps))).to(dev)
         pick, logq = _sample_choose(lp, temperature, top_k, top_p, u)
         g = lp.gather(1, pick.unsqueeze(1)).squeeze(1)
@@ -737,16 +750,8 @@ def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, 
 
 def _sample_result(toks, sum_logp, step_logp, step_logq, steps, end_idx, length_penalty, return_samples):
     """rules 6-7 over (B, n, >= steps + 1) samples"""
-    B, n = sum_logp.shape
     toks = toks[..., :steps + 1]
-    is_end = toks[..., 1:] == end_idx
-    before = (is_end.cumsum(-1) == 0).sum(-1)
-    n_k = torch.where(is_end.any(-1), before + 1, torch.full_like(before, steps))
-    final = sum_logp / ((5.0 + n_k.to(sum_logp.dtype)) / 6.0) ** length_penalty
-    best = torch.sort(-final, dim=1, stable=True).indices[:, 0]
-    rows = torch.arange(B, device=sum_logp.device)
-    m = int(n_k[rows, best].max()) if B else 0
-    out = toks[rows, best, :m + 1].clone()
+    out = _best_hypothesis(toks, sum_logp, steps, end_idx, length_penalty)[2]
     if not return_samples:
         return out
     return out, toks.clone(), sum_logp.clone(), step_logp[..., :steps].clone(), step_logq[..., :steps].clone()
@@ -762,18 +767,8 @@ class SampleDecoder(IncrementalDecoder):
     _cache_attr = "_sample_decoders"
 
     @classmethod
-    def for_batch(cls, agent, fs, max_len, start_idx, end_idx, pad_idx, n=1):
-        B, Tv = fs['rgb'].shape[:2]
-        Ta = fs['audio'].shape[1]
-        key = (B, -(-Tv // 64) * 64, -(-Ta // 64) * 64, int(max_len), int(start_idx), int(end_idx), int(pad_idx), int(n),
-               fs['rgb'].device)
-        cache = agent.__dict__.setdefault(cls._cache_attr, {})
-        dec = cache.get(key)
-        if dec is None:
-            if len(cache) >= 8:
-                cache.pop(next(iter(cache)))
-            dec = cache[key] = cls(agent, *key[:7], device=key[8], beams=key[7])
-        return dec
+    def _fits(cls, model, rows):
+        return rows <= ops.BEAM_MAX and 1 <= getattr(model, "voc_size", 0) <= ops.SAMPLE_MAX_V
 
     def __init__(self, agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device, beams=1, temperature=1.0,
                  top_k=0, top_p=1.0):
@@ -811,21 +806,14 @@ class SampleDecoder(IncrementalDecoder):
                         self.tok, self.out, self.sum_logp, self.step_logp, self.step_logq)
 
     def run(self, seed=0):
-        """-> (tokens (B, n, m + 1), sum_logp (B, n), step logp (B, n, m), step logq (B, n, m), m): the samples after the
-        step at which every row had finished"""
         s = int(seed) % _U64
         self.seed_word.fill_(s - _U64 if s >= 2 ** 63 else s)
-        for i in range(self.max_len):
-            self.step()
-            if (i + 1) % self.check_every == 0 and i + 1 < self.max_len and bool(self.done.all()):
-                break
-        m = self.steps_run
-        is_end = self.out[:, 1:m + 1] == self.end_idx
-        if m and bool(is_end.any(1).all()):
-            m = int(is_end.to(torch.uint8).argmax(1).max()) + 1
+        return super().run()
+
+    def result(self):
+        """(what run() returns) -> (tokens (B, n, m + 1), sum_logp (B, n), step logp (B, n, m), step logq (B, n, m), m): the
+        samples after the step at which every row had finished"""
+        m = self._steps_to_end()
         B, n = self.B, self.K
         return (self.out[:, :m + 1].reshape(B, n, m + 1).clone(), self.sum_logp.view(B, n).clone(),
                 self.step_logp[:, :m].reshape(B, n, m).clone(), self.step_logq[:, :m].reshape(B, n, m).clone(), m)
-
-    def result(self):
-        raise NotImplementedError("SampleDecoder: use run() (or sample_decode)")
