@@ -804,11 +804,15 @@ __global__ void scatter_add_rows_kernel(const float* __restrict__ dout, const in
 // ------------------------------------------------------------------------------------------------ Adam
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                            float gscale, const int32_t* __restrict__ step_dev) {
+                            float gscale, const int32_t* __restrict__ step_dev, const float* __restrict__ hyper) {
   if (step_dev) {  // step count lives on the device so a captured graph advances it between replays
     const float st = (float)step_dev[0];
     bc1 = 1.f - powf(b1, st);
     bc2_sqrt = sqrtf(1.f - powf(b2, st));
+  }
+  if (hyper) {     // the _dev entry points: learning rate and clip coefficient from the optimizer's hyper-parameter block
+    lr = hyper[0];
+    gscale *= hyper[2];
   }
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     float gi = g[i] * gscale;
@@ -988,11 +992,16 @@ __global__ __launch_bounds__(256) void fusion_tail_bwd_kernel(const float* __res
 constexpr int ADAM_WORDS = 7;
 __global__ void adam_segments_kernel(const int64_t* __restrict__ seg, int n_seg, float* __restrict__ p, const float* __restrict__ g,
                                      float* __restrict__ m, float* __restrict__ v, float lr, float b1, float b2, float eps,
-                                     float wd, float bc1, float bc2_sqrt, float gscale, const int32_t* __restrict__ step_dev) {
+                                     float wd, float bc1, float bc2_sqrt, float gscale, const int32_t* __restrict__ step_dev,
+                                     const float* __restrict__ hyper) {
   if (step_dev) {
     const float st = (float)step_dev[0];
     bc1 = 1.f - powf(b1, st);
     bc2_sqrt = sqrtf(1.f - powf(b2, st));
+  }
+  if (hyper) {     // bmhrl_adam_segments_dev: lr and the clip coefficient live in device words (ONE fp32 factor on the gradient)
+    lr = hyper[0];
+    gscale *= hyper[2];
   }
   int lo = 0, hi = n_seg - 1;
   while (lo < hi) {
@@ -1604,14 +1613,41 @@ extern "C" int bmhrl_scatter_add_rows(const float* dout, const int32_t* src, flo
   return hip_status(hipGetLastError());
 }
 
-extern "C" int bmhrl_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
-                               float beta1, float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev,
-                               float grad_scale, bmhrl_stream_t stream) {
+static int adam_step_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev, float grad_scale,
+                            const float* hyper, bmhrl_stream_t stream) {
   BMHRL_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && n > 0 && (step >= 1 || step_dev));
   const float bc1 = 1.f - powf(beta1, (float)step);
   const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, S_(stream), param, grad, exp_avg, exp_avg_sq,
-                     (long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, step_dev);
+                     (long)n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, step_dev, hyper);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int bmhrl_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                               float beta1, float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev,
+                               float grad_scale, bmhrl_stream_t stream) {
+  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, step_dev, grad_scale,
+                          nullptr, stream);
+}
+
+extern "C" int bmhrl_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                                   float beta1, float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev,
+                                   float grad_scale, const float* hyper, bmhrl_stream_t stream) {
+  BMHRL_CHECK_ARG(hyper);
+  return adam_step_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, step_dev, grad_scale,
+                          hyper, stream);
+}
+
+static int adam_segments_launch(const int64_t* segments, int32_t n_segments, int32_t n_blocks, float* param, const float* grad,
+                                float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, int32_t step, const int32_t* step_dev, float grad_scale, const float* hyper,
+                                bmhrl_stream_t stream) {
+  BMHRL_CHECK_ARG(segments && n_segments > 0 && n_blocks > 0 && param && grad && exp_avg && exp_avg_sq && (step >= 1 || step_dev));
+  const float bc1 = 1.f - powf(beta1, (float)step);
+  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+  hipLaunchKernelGGL(adam_segments_kernel, dim3((unsigned)n_blocks), dim3(256), 0, S_(stream), segments, n_segments, param, grad,
+                     exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, step_dev, hyper);
   return hip_status(hipGetLastError());
 }
 
@@ -1619,12 +1655,17 @@ extern "C" int bmhrl_adam_segments(const int64_t* segments, int32_t n_segments, 
                                    float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
                                    float weight_decay, int32_t step, const int32_t* step_dev, float grad_scale,
                                    bmhrl_stream_t stream) {
-  BMHRL_CHECK_ARG(segments && n_segments > 0 && n_blocks > 0 && param && grad && exp_avg && exp_avg_sq && (step >= 1 || step_dev));
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adam_segments_kernel, dim3((unsigned)n_blocks), dim3(256), 0, S_(stream), segments, n_segments, param, grad,
-                     exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, step_dev);
-  return hip_status(hipGetLastError());
+  return adam_segments_launch(segments, n_segments, n_blocks, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
+                              step, step_dev, grad_scale, nullptr, stream);
+}
+
+extern "C" int bmhrl_adam_segments_dev(const int64_t* segments, int32_t n_segments, int32_t n_blocks, float* param,
+                                       const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2,
+                                       float eps, float weight_decay, int32_t step, const int32_t* step_dev, float grad_scale,
+                                       const float* hyper, bmhrl_stream_t stream) {
+  BMHRL_CHECK_ARG(hyper);
+  return adam_segments_launch(segments, n_segments, n_blocks, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay,
+                              step, step_dev, grad_scale, hyper, stream);
 }
 
 extern "C" int bmhrl_make_masks(const float* rgb, int64_t ld_rgb, const float* audio, int64_t ld_aud, const int64_t* trg, int32_t B,

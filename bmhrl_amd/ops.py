@@ -563,9 +563,26 @@ def reinforce_bwd(probs, ld, action, value, critic_value, gscale, dprobs, dvalue
                                                _p(dcritic), rows, V, stream()), "bmhrl_reinforce_bwd")
 
 
-def adam_step(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, step_dev=None):
+def adam_step(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, step_dev=None,
+              hyper=None):
+    """hyper: the optimizer's hyper-parameter block (include/bmhrl_hip.h) -- the learning rate and the clip coefficient are
+    read from it on the device (bmhrl_adam_step_dev) and `lr` is not used"""
+    if hyper is not None:
+        _need_cuda(param, hyper)
+        _lib.check(_lib.load().bmhrl_adam_step_dev(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
+                                                   lr, beta1, beta2, eps, weight_decay, step, _p(step_dev), grad_scale,
+                                                   hyper.data_ptr(), stream()), "bmhrl_adam_step_dev")
+        return
     _lib.check(_lib.load().bmhrl_adam_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n, lr,
                                            beta1, beta2, eps, weight_decay, step, _p(step_dev), grad_scale, stream()), "bmhrl_adam_step")
+
+
+def grad_norm(table, n_segments, n_blocks, grad, grad_scale, partials, hyper):
+    """hyper[3] = L2 norm of the gradient the Adam table describes (x grad_scale), hyper[2] = the clip coefficient for the
+    threshold in hyper[1] (bmhrl_grad_norm in include/bmhrl_hip.h); partials: fp32 workspace, one element per block"""
+    _need_cuda(table, grad, partials, hyper)
+    _lib.check(_lib.load().bmhrl_grad_norm(table.data_ptr(), n_segments, n_blocks, grad.data_ptr(), grad_scale,
+                                           partials.data_ptr(), partials.numel(), hyper.data_ptr(), stream()), "bmhrl_grad_norm")
 
 
 def gemm_f32(A, W, bias1, bias2, C, M, N, K):
@@ -602,10 +619,16 @@ def critic_head(x, w, b, threshold, score, labels, rows, H):
 
 
 def adam_segments(table, n_segments, n_blocks, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step,
-                  grad_scale=1.0, step_dev=None):
+                  grad_scale=1.0, step_dev=None, hyper=None):
     """Adam over the flat bucket through a per-parameter table that also names each weight's bf16 shadow (see
-    bmhrl_adam_segments in include/bmhrl_hip.h)"""
-    _need_cuda(table, param)
+    bmhrl_adam_segments in include/bmhrl_hip.h); hyper: as adam_step (bmhrl_adam_segments_dev)"""
+    _need_cuda(table, param, hyper)
+    if hyper is not None:
+        _lib.check(_lib.load().bmhrl_adam_segments_dev(table.data_ptr(), n_segments, n_blocks, param.data_ptr(), grad.data_ptr(),
+                                                       exp_avg.data_ptr(), exp_avg_sq.data_ptr(), lr, beta1, beta2, eps,
+                                                       weight_decay, step, _p(step_dev), grad_scale, hyper.data_ptr(), stream()),
+                   "bmhrl_adam_segments_dev")
+        return
     _lib.check(_lib.load().bmhrl_adam_segments(table.data_ptr(), n_segments, n_blocks, param.data_ptr(), grad.data_ptr(),
                                                exp_avg.data_ptr(), exp_avg_sq.data_ptr(), lr, beta1, beta2, eps, weight_decay,
                                                step, _p(step_dev), grad_scale, stream()), "bmhrl_adam_segments")

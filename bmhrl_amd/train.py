@@ -29,7 +29,13 @@ class FlatAdam:
     """Adam over parameters re-homed into one flat fp32 buffer (views keep the nn.Parameter objects and the
     state-dict layout intact).  `params` that never receive a gradient keep a zero slot."""
 
-    def __init__(self, params: List[torch.nn.Parameter], lr: float, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, params: List[torch.nn.Parameter], lr: float, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 grad_clip: Optional[float] = None, lr_on_device: bool = False):
+        """grad_clip: clip() scales the gradient so that its global L2 norm is at most this (torch.nn.utils.clip_grad_norm_);
+        it implies lr_on_device.  lr_on_device: the learning rate (and the clip threshold / coefficient) live in the
+        hyper-parameter block `hyper` in device memory (include/bmhrl_hip.h), which the optimizer launch reads: set_lr() /
+        set_grad_clip() then also reach a step that has been captured.  Both off (the default): no block, the launches take
+        lr by value as they always did."""
         self.params = [p for p in params]
         self.params0 = list(self.params)          # construction order (in_param_order)
         dev = self.params[0].device
@@ -48,8 +54,21 @@ class FlatAdam:
             self.flat[o:o + s].copy_(p.data.reshape(-1))
             p.data = self.flat[o:o + s].view(p.shape)
         self.grad_views = [self.grad[o:o + s].view(p.shape) for p, o, s in zip(self.params, self.offsets, self.sizes)]
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self._lr, self.betas, self.eps, self.weight_decay = float(lr), betas, eps, weight_decay
         self.step_count = 0
+        self.captured = False          # set by CaptionTrainer.capture(): a captured launch holds lr by value unless lr_on_device
+        self.grad_clip = None if grad_clip is None else float(grad_clip)
+        self.hyper = None
+        if grad_clip is not None or lr_on_device:
+            # allocated once: a captured step holds its address, so it lives with the optimizer (as CaptionTrainer.seed_dev)
+            inf = float("inf")
+            self.hyper = torch.tensor([self._lr, inf if grad_clip is None else self.grad_clip, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0],
+                                      dtype=torch.float32).to(dev)
+        if grad_clip is not None:
+            blocks = sum((sz + ops.SEG_ELEMS_PER_BLOCK - 1) // ops.SEG_ELEMS_PER_BLOCK for sz in self.sizes)
+            self._norm_ws = torch.zeros(max(1, blocks), device=dev)          # one fp32 partial per block of the norm launch
+            # the table clip() uses while no per-parameter plan exists: the flat bucket as one segment
+            self._flat_seg = torch.tensor([[0, 0, 1, n, 0, 0, 0]], dtype=torch.int64).to(dev)
         # shadows (bf16 copies of weights, functional.ShadowCache) of these parameters: `generation` moves with every update
         # -- also with every replay of a captured step, which no host code sees -- and `maintained` names the shadow entries
         # the Adam pass writes itself; every other entry that involves one of these parameters is stale after an update
@@ -63,6 +82,60 @@ class FlatAdam:
     def zero_grad(self):
         for p in self.params:
             p.grad = None
+
+    # ------------------------------------------------------------------ learning rate / clipping
+    @property
+    def lr(self) -> float:
+        """what was last set (the host's copy: no read-back from the device)"""
+        return self._lr
+
+    @lr.setter
+    def lr(self, value: float):
+        self.set_lr(value)
+
+    def set_lr(self, lr: float):
+        """With lr_on_device an in-place write of the block's word on the current stream: no synchronisation, and a captured
+        step sees it at its next replay.  Without it the launches take lr by value, so a captured step cannot follow."""
+        if self.hyper is None and self.captured:
+            raise RuntimeError("set_lr: this optimizer's step has been captured with the learning rate as a launch constant; "
+                               "the change would be ignored.  Build the optimizer / trainer with lr_on_device=True")
+        self._lr = float(lr)
+        if self.hyper is not None:
+            self.hyper[0:1].fill_(self._lr)
+
+    def set_grad_clip(self, max_norm: Optional[float]):
+        """new clip threshold (None: nothing clips, the coefficient is exactly 1); the norm launch reads it on the device"""
+        if self.grad_clip is None:
+            raise RuntimeError("set_grad_clip: this optimizer was built without grad_clip (its step has no norm launch)")
+        self.grad_clip = float("inf") if max_norm is None else float(max_norm)
+        self.hyper[1:2].fill_(self.grad_clip)
+
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """global L2 norm found by the last clip(): a view of the block's word (device tensor, no synchronisation)"""
+        return self.hyper[3]
+
+    @property
+    def last_clip_coef(self) -> torch.Tensor:
+        return self.hyper[2]
+
+    def clip(self, grad_scale: float = 1.0):
+        """Norm of the gradient x grad_scale (all of it: after gather_grads() and the all-reduce) and the clip coefficient
+        into the hyper-parameter block; the step() / step_part() that follows multiplies the gradient by it."""
+        if self.grad_clip is None:
+            raise RuntimeError("clip: this optimizer was built without grad_clip")
+        if not self.flat.is_cuda:      # host-side form (gloo tests): the same rules in torch ops, fp64 sum
+            norm = (self.grad * torch.tensor(grad_scale, dtype=torch.float32)).double().pow(2).sum().sqrt().float()
+            coef = torch.clamp((norm + 1e-6).reciprocal() * self.hyper[1], max=1.0)
+            self.hyper[2] = coef if bool(torch.isfinite(norm)) else float("nan")
+            self.hyper[3] = norm
+            return
+        plan = self._segment_plan() if self.fused_shadows else None
+        if plan is None:               # no table (yet): gather_grads() left every gradient in the flat bucket -- one segment
+            table, n_seg, n_blk = self._flat_seg, 1, (self.n + ops.SEG_ELEMS_PER_BLOCK - 1) // ops.SEG_ELEMS_PER_BLOCK
+        else:
+            table, n_seg, n_blk = plan[:3]
+        ops.grad_norm(table, n_seg, n_blk, self.grad, grad_scale, self._norm_ws, self.hyper)
 
     direct_grads = os.environ.get("BMHRL_DIRECT_GRADS", "1") == "1"   # one rank: Adam reads the gradients in place (no gather)
 
@@ -356,7 +429,7 @@ class FlatAdam:
         table, n_seg, n_blk = self._part_plans[part]
         if n_seg:
             ops.adam_segments(table, n_seg, n_blk, self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.lr, b1, b2, self.eps,
-                              self.weight_decay, self.step_count, grad_scale, step_dev=self.step_dev)
+                              self.weight_decay, self.step_count, grad_scale, step_dev=self.step_dev, hyper=self.hyper)
         if (part == len(self._part_plans) - 1) if last is None else last:
             for kind, key in self._seg_plan[1][3]:
                 SHADOWS.mark_stale(kind, key)
@@ -373,18 +446,21 @@ class FlatAdam:
             plan = self._segment_plan() if self.fused_shadows else None
             if plan is None:
                 ops.adam_step(self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.n, self.lr, b1, b2, self.eps,
-                              self.weight_decay, self.step_count, grad_scale, step_dev=self.step_dev)
+                              self.weight_decay, self.step_count, grad_scale, step_dev=self.step_dev, hyper=self.hyper)
             else:
                 # the update also writes the bf16 shadows (and concatenated-bias copies) of the weights it owns: they stay
                 # current without the per-step refresh pass; shadows it could not place (a parameter in two groups) go stale
                 table, n_seg, n_blk, uncovered = plan
                 ops.adam_segments(table, n_seg, n_blk, self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.lr, b1, b2,
-                                  self.eps, self.weight_decay, self.step_count, grad_scale, step_dev=self.step_dev)
+                                  self.eps, self.weight_decay, self.step_count, grad_scale, step_dev=self.step_dev,
+                                  hyper=self.hyper)
                 for kind, key in uncovered:
                     SHADOWS.mark_stale(kind, key)
                 return
         else:  # host-side reference used by the gloo tests of the data-parallel plumbing (no model arithmetic)
             g = self.grad * grad_scale
+            if self.grad_clip is not None:      # ONE fp32 factor, as the device form: grad_scale x the coefficient of clip()
+                g = self.grad * (torch.tensor(grad_scale, dtype=torch.float32) * self.hyper[2])
             if self.weight_decay:
                 g = g + self.weight_decay * self.flat
             self.exp_avg.mul_(b1).add_(g, alpha=1 - b1)
@@ -393,6 +469,33 @@ class FlatAdam:
             bc2 = 1 - b2 ** self.step_count
             self.flat.addcdiv_(self.exp_avg, (self.exp_avg_sq.sqrt() / bc2 ** 0.5).add_(self.eps), value=-self.lr / bc1)
         SHADOWS.invalidate()   # bf16 weight shadows are stale now
+
+
+class PlateauLR:
+    """torch.optim.lr_scheduler.ReduceLROnPlateau (mode "min", relative threshold, cooldown 0) for a trainer or optimizer
+    with set_lr(): the reference driver's scheduler line (scripts/train_rl_captioning_module.py:85-88) in a form that also
+    reaches a captured step.  step(metric) after every validation."""
+
+    def __init__(self, trainer, factor: float = 0.1, patience: int = 10, threshold: float = 1e-4, min_lr: float = 0.0,
+                 eps: float = 1e-8):
+        assert factor < 1.0
+        self.trainer, self.factor, self.patience, self.threshold, self.min_lr, self.eps = trainer, factor, patience, threshold, min_lr, eps
+        self.best, self.bad = float("inf"), 0
+        self.lr = float(trainer.opt.lr)
+
+    def step(self, metric) -> float:
+        m = float(metric)
+        if m < self.best * (1.0 - self.threshold):
+            self.best, self.bad = m, 0
+        else:
+            self.bad += 1
+        if self.bad > self.patience:
+            new = max(self.lr * self.factor, self.min_lr)
+            if self.lr - new > self.eps:
+                self.lr = new
+                self.trainer.set_lr(new)
+            self.bad = 0
+        return self.lr
 
 
 def token_weight(n_local: torch.Tensor, group=None) -> torch.Tensor:
@@ -430,8 +533,13 @@ class CaptionTrainer:
 
     def __init__(self, cfg, voc_size: int, device, lr: float = 1e-4, weight_decay: float = 0.0, seed: int = 0,
                  critic_state: Optional[Dict[str, torch.Tensor]] = None, pad_idx: int = 1, smoothing: float = 0.7,
-                 phase: str = "warmstart", reward_fn=None, value_lr: float = 1e-4, exploration: Optional[bool] = None):
-        """phase: "warmstart" (label-smoothing KL, reference :1132-1189), "worker" or "manager" (the RL step of
+                 phase: str = "warmstart", reward_fn=None, value_lr: float = 1e-4, exploration: Optional[bool] = None,
+                 grad_clip: Optional[float] = None, lr_on_device: bool = False):
+        """grad_clip (default: cfg.grad_clip): the captioning bucket's averaged gradient is scaled to this global L2 norm
+        between the all-reduce and the update (FlatAdam.clip; the value network is not clipped, as the reference clips
+        cap_model.parameters() only); it implies lr_on_device.  lr_on_device: both optimizers read their learning rate from
+        device words, so set_lr() / set_value_lr() (and PlateauLR) also reach a captured step.
+        phase: "warmstart" (label-smoothing KL, reference :1132-1189), "worker" or "manager" (the RL step of
         train_bimodal_bl, reference :797-890: biased KL with sampled / arg-max tokens and their rewards + the value head's
         masked-MSE update; the phase decides which modules are trainable, teach_worker / teach_manager :572-589).
         reward_fn(sampled (B, L), captions) -> (B, L) rewards (BASELINE configs[2]: synthetic).
@@ -440,6 +548,10 @@ class CaptionTrainer:
         False switches the manager's Gaussian goal vector off (comparisons with the CPU oracle, which cannot draw it)."""
         assert phase in ("warmstart", "worker", "manager")
         self.phase = phase
+        if grad_clip is None:
+            grad_clip = getattr(cfg, "grad_clip", None)
+        self.grad_clip = grad_clip
+        lr_on_device = bool(lr_on_device) or grad_clip is not None
         self.reward_fn = reward_fn
         cfg.device = str(device)
         ds = SimpleNamespace(trg_voc_size=voc_size, train_vocab=SimpleNamespace(vectors=None))
@@ -467,7 +579,7 @@ class CaptionTrainer:
             vshapes = {k: tuple(v.shape) for k, v in self.value_net.state_dict().items()}
             self.value_net.load_state_dict(syn.fill_state_dict(vshapes, seed=seed + 7))
             self.value_net.to(self.device)
-            self.vopt = FlatAdam(list(self.value_net.parameters()), lr=value_lr)
+            self.vopt = FlatAdam(list(self.value_net.parameters()), lr=value_lr, lr_on_device=lr_on_device)
         self.stabilize = bool(getattr(cfg, "rl_stabilize", False))
         self.pad_idx = pad_idx
         self.criterion = LabelSmoothing(smoothing, pad_idx)
@@ -489,7 +601,8 @@ class CaptionTrainer:
         late = [p for p in early if names[id(p)].startswith("emb_C.")]
         early = [p for p in early if not names[id(p)].startswith("emb_C.")] + late
         self.phase_params = [early] + [per_layer[i] for i in reversed(range(n_enc))]
-        self.opt = FlatAdam([p for ph in self.phase_params for p in ph], lr=lr, weight_decay=weight_decay)
+        self.opt = FlatAdam([p for ph in self.phase_params for p in ph], lr=lr, weight_decay=weight_decay, grad_clip=grad_clip,
+                            lr_on_device=lr_on_device)
         self.opt.set_buckets([len(ph) for ph in self.phase_params])
         # parts of the optimizer pass: [head + fusion stacks | caption embedding | encoder layer N-1 | ... | encoder layer 0]
         pb = [0, len(early) - len(late), len(early)]
@@ -514,6 +627,11 @@ class CaptionTrainer:
         # 4.953 / 4.916 ms with it, 4.897 / 4.926 ms without -- nothing: the chip is full during the encoder backward, so the
         # 0.29 ms of HBM-bound update moved beside it is added to it, not hidden.  Off by default.
         self.early_adam = os.environ.get("BMHRL_EARLY_ADAM", "0") == "1"
+        if grad_clip is not None and (self.phased_adam or self.early_adam):
+            # clipping needs the whole gradient before any part of the update runs
+            import warnings
+            warnings.warn("grad_clip is set: BMHRL_PHASED_ADAM / BMHRL_EARLY_ADAM are ignored")
+            self.phased_adam = self.early_adam = False
         self._early_armed = False
         self._early_pending = {}
         self._early_done = set()
@@ -534,6 +652,24 @@ class CaptionTrainer:
         # trainer's constructor left the first trainer's graph bumping freed memory
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
         SEEDS.dev = self.seed_dev
+
+    # ------------------------------------------------------------------ learning rate / clipping
+    def set_lr(self, lr: float):
+        self.opt.set_lr(lr)
+
+    def set_value_lr(self, lr: float):
+        self.vopt.set_lr(lr)
+
+    def set_grad_clip(self, max_norm: Optional[float]):
+        self.opt.set_grad_clip(max_norm)
+
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        return self.opt.last_grad_norm
+
+    @property
+    def last_clip_coef(self) -> torch.Tensor:
+        return self.opt.last_clip_coef
 
     # ------------------------------------------------------------------ one step, eager
     def _head(self, fs, captions):
@@ -661,6 +797,8 @@ class CaptionTrainer:
         SCRATCH.end_step()
         scale = self.opt.all_reduce()
         adv = captions.is_cuda
+        if self.grad_clip is not None:
+            self.opt.clip(scale)                  # norm of the averaged gradient: every rank computes it from identical bytes
         self.opt.step(scale, dev_step_advanced=adv)
         self._plan_clean = self.scratch.last_spill == 0
         if self.value_net is not None:
@@ -690,7 +828,7 @@ class CaptionTrainer:
     def _early_ok(self) -> bool:
         o = self.opt
         plan = o.__dict__.get("_seg_plan")
-        return (self.early_adam and self.device.type == "cuda" and self._world_scale() == 1.0 and not self._split()
+        return (self.early_adam and self.grad_clip is None and self.device.type == "cuda" and self._world_scale() == 1.0 and not self._split()
                 and o.direct_grads and o.fused_shadows and not o.__dict__.get("_homes", False)
                 and plan is not None and plan[2] is not None and len(o.__dict__.get("_part_plans", ())) == self.n_enc + 2
                 and self.__dict__.get("_plan_clean", False) and self.scratch.last_spill == 0
@@ -771,6 +909,9 @@ class CaptionTrainer:
         self.static = {k: v.clone() for k, v in fs.items()}
         self.static["captions"] = captions.clone()
         self.static_loss = torch.zeros((), device=self.device)
+        for o in (self.opt, getattr(self, "vopt", None)):
+            if o is not None:
+                o.captured = True
         self.opt.phased_direct = self._phased_one_rank()
         s = self._warm_stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -872,7 +1013,7 @@ class CaptionTrainer:
         return self._world_scale() != 1.0
 
     def _phased_one_rank(self) -> bool:
-        return self.phased_adam and self.split_backward is None and self._world_scale() == 1.0 and self.device.type == "cuda" \
+        return self.phased_adam and self.grad_clip is None and self.split_backward is None and self._world_scale() == 1.0 and self.device.type == "cuda" \
             and self.opt.direct_grads and self.opt.fused_shadows and os.environ.get("BMHRL_SPLIT_BACKWARD") is None
 
     def _split(self) -> bool:
@@ -974,6 +1115,8 @@ class CaptionTrainer:
             if self.value_net is not None:
                 self.vopt.step(scale, dev_step_advanced=True)
             return
+        if self.grad_clip is not None:
+            self.opt.clip(scale)
         self.opt.step(scale, dev_step_advanced=True)              # (the counters moved in the step's first launch: _head)
         # the table this pass (re)built reads the gradients where THIS pass left them: valid for the next pass when all of them
         # came out of the scratch arenas (a deterministic bump allocator) -- what _early_ok() asks for

@@ -491,6 +491,33 @@ int bmhrl_adam_segments(const int64_t* segments, int32_t n_segments, int32_t n_b
                         float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
                         float weight_decay, int32_t step, const int32_t* step_dev, float grad_scale, bmhrl_stream_t stream);
 
+/* Hyper-parameter block of an optimizer (train.FlatAdam.hyper): 8 fp32 words in device memory, so that a captured step
+ * follows a change of the learning rate or of the clip threshold without being captured again.
+ *   [0] lr        [1] max_norm (clip threshold)        [2] coef (written by bmhrl_grad_norm; 1.0 when nothing clips)
+ *   [3] norm (written by bmhrl_grad_norm)              [4..7] reserved, zero
+ *
+ * bmhrl_grad_norm: global L2 norm of the gradient that `segments` describes -- the table of bmhrl_adam_segments: word 6 is
+ * the gradient's address, 0 = grad + offset; the shadow words are not read -- scaled by grad_scale, and the clip coefficient
+ * of torch.nn.utils.clip_grad_norm_(norm_type = 2):
+ *   hyper[3] = norm = sqrt(sum over every element of (g * grad_scale)^2)
+ *   hyper[2] = coef = min(1, max_norm / (norm + 1e-6)) with max_norm = hyper[1], read on the device (the quotient formed as
+ *              torch forms it, reciprocal(norm + 1e-6) * max_norm, in fp32); NaN when the norm is not finite.
+ * Two launches in a fixed summation order (csrc/grad_norm.hip), no floating-point atomics: the two words are the same
+ * bits in every run.  partials: fp32 workspace of partials_elems >= n_blocks elements, one per block. */
+int bmhrl_grad_norm(const int64_t* segments, int32_t n_segments, int32_t n_blocks, const float* grad, float grad_scale,
+                    float* partials, int64_t partials_elems, float* hyper, bmhrl_stream_t stream);
+
+/* bmhrl_adam_step / bmhrl_adam_segments with the learning rate and the clip coefficient read from the block: lr = hyper[0]
+ * (the lr argument is not used) and the gradient is multiplied by the ONE fp32 factor grad_scale * hyper[2].  Bit-equal to
+ * the entry point above called with that lr and that product as grad_scale. */
+int bmhrl_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, int32_t step, const int32_t* step_dev,
+                        float grad_scale, const float* hyper, bmhrl_stream_t stream);
+int bmhrl_adam_segments_dev(const int64_t* segments, int32_t n_segments, int32_t n_blocks, float* param, const float* grad,
+                            float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int32_t step, const int32_t* step_dev, float grad_scale, const float* hyper,
+                            bmhrl_stream_t stream);
+
 /* The masks of a bimodal step in one launch (model/masking.py:18-55): v_mask[b][t] = rgb[b][t][0] != 0 (row stride ld_rgb
  * elements), a_mask likewise from audio, c_mask[b][i][j] = trg[b][j] != pad_idx && j <= i; bytes 0 / 1, each mask written
  * `copies` times back to back ((copies, B, .) layout). */
