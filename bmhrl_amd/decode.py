@@ -14,6 +14,8 @@ Three forms, same tokens:
 beam_decode / beam_decoder: beam search over the same token step on B*K rows (BeamDecoder), or over full re-runs.
 sample_decode / sample_decoder: temperature / top-k / top-p sampling, n samples per clip, over the same token step on B*n rows
 (SampleDecoder), or over full re-runs.
+Every decoder takes no_repeat_ngram / min_len / repetition_penalty (the constraints section): the rules edit the step's
+log-probs before the choice, in the captured step through one HIP launch.
 """
 import math
 import random
@@ -28,17 +30,21 @@ _BF16 = torch.bfloat16
 
 
 def greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, return_first=False, memoise=True,
-                  incremental=None):
+                  incremental=None, no_repeat_ngram=0, min_len=0, repetition_penalty=1.0):
     """memoise=True (default) runs the encoder and the fusion layers' memory projections once per clip batch instead of
     once per generated token; the tokens and log-probs are the same as with the reference's full re-run (memoise=False).
     incremental (default: on for the HIP agent in eval mode on a GPU with both modalities) additionally decodes through
-    IncrementalDecoder.  Models without encode_memory() (anything but the HIP BMHrlAgent) always take the full re-run."""
+    IncrementalDecoder.  Models without encode_memory() (anything but the HIP BMHrlAgent) always take the full re-run.
+    no_repeat_ngram / min_len / repetition_penalty: the constraints section's rules, on every path; with a rule set,
+    return_first returns the first step's adjusted log-probs, and a max_len + 1 above ops.LOGIT_RULES_MAX_HIST (256, the
+    kernel's history capacity) takes the re-run path."""
+    rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty, max_len)
     with torch.no_grad():
         B = feature_stacks['audio'].shape[0]
         device = feature_stacks['audio'].device
         memoise = memoise and hasattr(model, "encode_memory") and not model.training
         dec = _incremental(IncrementalDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx,
-                           incremental=incremental if memoise else False)
+                           incremental=incremental if memoise else False, rules=rules)
         if dec is not None:
             return dec.run(return_first)
         done = torch.zeros(B, 1, dtype=torch.bool, device=device)
@@ -54,6 +60,8 @@ def greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, m
                 last = model.inference_from_memory(memory, trg, masks, kv_cache)[:, -1]
             else:
                 last = _rerun_logp(model, x, rep, trg, modality, pad_idx)
+            if rules is not None:
+                last = _apply_rules(last.float(), trg, trg.size(-1) - 1, *rules, end_idx, pad_idx)
             if first is None:
                 first = last.clone()
             nxt = last.argmax(dim=-1, keepdim=True)
@@ -62,17 +70,22 @@ def greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, m
     return (trg, first) if return_first else trg
 
 
-def _incremental(cls, model, fs, modality, max_len, start_idx, end_idx, pad_idx, rows=1, incremental=None, params=None):
+def _incremental(cls, model, fs, modality, max_len, start_idx, end_idx, pad_idx, rows=1, incremental=None, params=None,
+                 rules=None):
     """the decoder of class `cls` (`rows` rows per clip) with the clip batch begun, or None: take the re-run path.
-    incremental=None: the class's `enabled`; params: SampleDecoder.set_params arguments, set before begin()"""
+    incremental=None: the class's `enabled`; params: SampleDecoder.set_params arguments, rules: what _rule_args returned
+    (IncrementalDecoder.set_rules arguments, None: all off), both set before begin()"""
     if incremental is None:
         incremental = cls.enabled
     if not (incremental and hasattr(model, "encode_memory") and not model.training and fs['audio'].device.type == "cuda"
             and modality == "audio_video" and max_len >= 1 and cls._fits(model, rows)):
         return None
+    if rules is not None and max_len + 1 > ops.LOGIT_RULES_MAX_HIST:
+        return None
     dec = cls.for_batch(model, fs, max_len, start_idx, end_idx, pad_idx, rows)
     if params is not None:
         dec.set_params(*params)
+    dec.set_rules(*(rules or _NO_RULES))
     return dec if dec.begin(fs) else None
 
 
@@ -91,6 +104,18 @@ def _rerun_logp(model, x, rep, hist, modality, pad_idx):
 
 def bimodal_decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
     return greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality)
+
+
+def greedy_decoder(no_repeat_ngram=0, min_len=0, repetition_penalty=1.0):
+    """a greedy decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality)
+    under the constraints section's rules, e.g. validation_1by1_loop(cfg, model, loader, greedy_decoder(3, min_len=5), epoch,
+    TBoard)"""
+    rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty) or _NO_RULES
+
+    def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
+        return greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, no_repeat_ngram=rules[0],
+                             min_len=rules[1], repetition_penalty=rules[2])
+    return decoder
 
 
 bmhrl_greedy_decoder = bimodal_decoder
@@ -190,6 +215,7 @@ class IncrementalDecoder:
         self.graph = None
         self._shadow_sig = None
         self.steps_run = 0
+        self.rules = None               # set_rules: (no_repeat_ngram, min_len, repetition_penalty) while a rule is set
         self._init_search()
         with torch.no_grad():
             self._reset()
@@ -200,6 +226,33 @@ class IncrementalDecoder:
 
     def _init_search(self):
         """buffers of the token choice (greedy: none beyond `out` / `done`)"""
+
+    def set_rules(self, no_repeat_ngram=0, min_len=0, repetition_penalty=1.0):
+        """the constraints section's rules for the decodes that follow; they are launch arguments, so the step is captured
+        again when they change (the first decode under rules on a new shape therefore captures twice: __init__ without
+        rules, then here).  Not while a clip batch is being decoded.  The rules stay on the decoder, as SampleDecoder's
+        set_params values do: whoever takes the cached decoder from for_batch directly inherits what the last caller set --
+        _incremental sets them before every clip batch, the defaults included."""
+        rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty, self.max_len)
+        if rules is not None and self.max_len + 1 > ops.LOGIT_RULES_MAX_HIST:
+            raise ValueError(f"set_rules: a history of {self.max_len + 1} tokens exceeds {ops.LOGIT_RULES_MAX_HIST}")
+        if rules != self.rules:
+            self.rules = rules
+            if self.graph is not None:
+                if rules is not None:
+                    # eager once: the kernel's first launch is not one under capture.  It edits self.logp and reads self.t
+                    # and self.out as the last decode left them; begin() resets all three before they are used again
+                    self._constrain()
+                self._capture()
+
+    def _constrain(self):
+        """rules 1-3 on self.logp, rows' sequences from self.out.  An end_idx that is no token id (callers that never stop)
+        leaves rule 3 nothing to ban."""
+        n, m, theta = self.rules
+        V = self.logp.shape[-1]
+        ends = 0 <= self.end_idx < V
+        ops.logit_rules(self.logp, V, self.R, V, self.out, self.t, n, m if ends else 0, theta,
+                        self.end_idx if ends else self.pad_idx, self.pad_idx)
 
     # ------------------------------------------------------------------ per clip
     def _reset(self):
@@ -242,7 +295,8 @@ class IncrementalDecoder:
         return True
 
     def run(self, return_first=False):
-        """steps until max_len or, looked at every check_every tokens, until everything has finished -> result()"""
+        """steps until max_len or, looked at every check_every tokens, until everything has finished -> result();
+        return_first: also the first step's log-probs (the adjusted ones while a rule is set)"""
         first = None
         for i in range(self.max_len):
             self.step()
@@ -403,6 +457,9 @@ class IncrementalDecoder:
         logp = WorkerHeadFn.apply(w_feat.view(B, 1, -1), gc.view(B, 1, -1), ag.worker.core.projection.weight,
                                   ag.worker.core.projection.bias)
         self.logp.copy_(logp)
+        if self.rules is not None:
+            self._constrain()
+            logp = self.logp
         self._choose(logp)
         t.add_(1)
 
@@ -413,6 +470,70 @@ class IncrementalDecoder:
         self.out.index_copy_(1, t + 1, nxt.view(B, 1))
         self.done.logical_or_(nxt == self.end_idx)
         self.tok.copy_(nxt)
+
+
+# ---------------------------------------------------------------------------------------------------------- constraints
+# Rules (both paths -- bmhrl_logit_rules in the captured token step, _apply_rules in the re-runs -- implement exactly
+# these).  Inputs: no_repeat_ngram = n >= 0, min_len = m >= 0, repetition_penalty = theta (finite, > 0; the fp32 value of
+# the host float).  A row's sequence at step t is s = out[row, 0..t]: the start token and the t tokens generated so far
+# (a beam's own history; pad_idx after a finished row's end).  lp: the model's fp32 log-probs of that row (V values).
+#  1. penalty.  theta != 1: for every distinct token id v of s with v != pad_idx, lp[v] = lp[v] * theta -- one fp32 multiply,
+#     once per id however often it occurs.  Log-probs are <= 0, so theta > 1 lowers them;
+#  2. n-gram ban.  n >= 1 and t + 1 >= n: for every j in [0, t + 1 - n] with s[j .. j+n-2] == s[t-n+2 .. t],
+#     lp[s[j+n-1]] = -inf.  The compared slice is empty for n = 1: every token of s is banned.  t + 1 < n: nothing is;
+#  3. minimum length.  t < m: lp[end_idx] = -inf (an end_idx that is no token id, e.g. -1 for "never stop": nothing);
+#  4. the adjusted lp replaces the model's log-probs in everything downstream, without renormalising: the greedy arg-max,
+#     beam rules 2-3 (scores are sums of adjusted values), sampling rules 2-5 (q, the recorded step_logp / sum_logp and
+#     step_logq are computed from adjusted values).  A row whose every entry is -inf falls under the choosers' own rules for
+#     such rows (arg-max: token 0);
+#  5. with n = 0, m = 0, theta = 1 nothing is touched and the token step has no launch more than without this section.
+#     Finished rows are adjusted like live ones; their choice ignores lp already.
+# A token id of s outside [0, V) takes part in the comparisons of rule 2 but selects no entry of lp.
+# Refused with ValueError: n < 0, m < 0, n or m not an integer, theta non-finite or <= 0, m > max_len.
+
+_NO_RULES = (0, 0, 1.0)
+
+
+def _rule_args(no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, max_len=None):
+    """(n, m, theta as the fp32 value the kernel sees) of valid arguments, None when they are the defaults (no rule set)"""
+    for name, v in (("no_repeat_ngram", no_repeat_ngram), ("min_len", min_len)):
+        try:
+            whole = not isinstance(v, bool) and int(v) == v
+        except (TypeError, ValueError, OverflowError):
+            whole = False
+        if not whole:
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    n, m, theta = int(no_repeat_ngram), int(min_len), float(repetition_penalty)
+    if n < 0:
+        raise ValueError(f"no_repeat_ngram must be >= 0, got {no_repeat_ngram}")
+    if m < 0 or (max_len is not None and m > max_len):
+        raise ValueError(f"min_len must lie in [0, max_len], got {min_len}")
+    if not (math.isfinite(theta) and theta > 0 and math.isfinite(_f32(theta)) and _f32(theta) > 0):
+        raise ValueError(f"repetition_penalty must be finite and > 0, got {repetition_penalty}")
+    rules = (n, m, _f32(theta))
+    return None if rules == _NO_RULES else rules
+
+
+def _apply_rules(lp, hist, t, ngram, min_len, penalty, end_idx, pad_idx):
+    """rules 1-3 in fp32 torch ops: lp (R, V) fp32 log-probs, hist (R, >= t + 1) int64 sequences -> the adjusted (R, V)"""
+    R, V = lp.shape
+    s = hist[:, :t + 1]
+    neg = torch.full_like(lp, float("-inf"))
+    entry = lambda ids: ((ids >= 0) & (ids < V), ids.clamp(0, V - 1))     # ids outside [0, V) select no entry of lp
+    if penalty != 1:
+        ok, idx = entry(s)
+        seen = torch.zeros(R, V, dtype=torch.int32, device=lp.device).scatter_add_(1, idx, (ok & (s != pad_idx)).to(torch.int32)) > 0
+        lp = torch.where(seen, lp * torch.tensor(penalty, dtype=lp.dtype, device=lp.device), lp)
+    if ngram >= 1 and t + 1 >= ngram:
+        grams = s.unfold(1, ngram, 1)                                         # (R, t + 2 - n, n): s[j .. j+n-1]
+        match = (grams[..., :ngram - 1] == s[:, t + 2 - ngram:].unsqueeze(1)).all(-1)
+        ok, idx = entry(grams[..., -1])
+        banned = torch.zeros(R, V, dtype=torch.int32, device=lp.device).scatter_add_(1, idx, (match & ok).to(torch.int32)) > 0
+        lp = torch.where(banned, neg, lp)
+    if t < min_len and 0 <= end_idx < V:
+        lp = lp.clone()
+        lp[:, end_idx] = float("-inf")
+    return lp
 
 
 # ---------------------------------------------------------------------------------------------------------- beam search
@@ -431,37 +552,45 @@ class IncrementalDecoder:
 
 
 def beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, beam_size=4, length_penalty=0.0,
-                return_scores=False, return_beams=False, incremental=None):
+                return_scores=False, return_beams=False, incremental=None, no_repeat_ngram=0, min_len=0,
+                repetition_penalty=1.0):
     """Beam search with the reference decoder's arguments.  Returns tokens (B, n + 1) int64, then -- when asked -- the
     chosen hypotheses' raw scores (B,) fp32, then all K hypotheses sorted best first as tokens (B, K, m + 1) (m: the
     longest n_k of all of them, so that no hypothesis is cut) and raw scores (B, K).
     incremental (default: on under the conditions greedy_decode takes IncrementalDecoder, and K <= min(16, V)) decodes
     through BeamDecoder; otherwise, or with incremental=False, every step re-runs model.inference over the (B*K)-row prefix
-    batch (any model with `inference`, CPU included)."""
+    batch (any model with `inference`, CPU included).  no_repeat_ngram / min_len / repetition_penalty: the constraints
+    section's rules; the scores are then sums of adjusted log-probs, and a max_len + 1 above ops.LOGIT_RULES_MAX_HIST (256)
+    takes the re-run path."""
     K = int(beam_size)
     if K < 1:
         raise ValueError(f"beam_size must be >= 1, got {beam_size}")
+    rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty, max_len)
     with torch.no_grad():
-        dec = _incremental(BeamDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, K, incremental)
+        dec = _incremental(BeamDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, K, incremental,
+                           rules=rules)
         found = dec.run() if dec is not None else _beam_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
-                                                              modality, K)
+                                                              modality, K, rules)
         return _beam_result(*found, end_idx, length_penalty, return_scores, return_beams)
 
 
-def beam_decoder(beam_size=4, length_penalty=0.0):
+def beam_decoder(beam_size=4, length_penalty=0.0, no_repeat_ngram=0, min_len=0, repetition_penalty=1.0):
     """a decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality), e.g.
     validation_1by1_loop(cfg, model, loader, beam_decoder(4), epoch, TBoard)"""
     if int(beam_size) < 1:
         raise ValueError(f"beam_size must be >= 1, got {beam_size}")
+    rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty) or _NO_RULES
 
     def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
         return beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, beam_size=beam_size,
-                           length_penalty=length_penalty)
+                           length_penalty=length_penalty, no_repeat_ngram=rules[0], min_len=rules[1],
+                           repetition_penalty=rules[2])
     return decoder
 
 
-def _beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K):
-    """rules 1-4 over full re-runs of model.inference on the prefix batch -> (tokens (B, K, n + 1), scores (B, K), n)"""
+def _beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K, rules=None):
+    """rules 1-4 over full re-runs of model.inference on the prefix batch -> (tokens (B, K, n + 1), scores (B, K), n);
+    rules: what _rule_args returned"""
     B = fs['audio'].shape[0]
     dev = fs['audio'].device
     rep, x = _rerun_setup(fs, K)
@@ -473,6 +602,8 @@ def _beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K):
     steps = 0
     while steps < max_len:
         lp = _rerun_logp(model, x, rep, hist, modality, pad_idx)
+        if rules is not None:
+            lp = _apply_rules(lp, hist, steps, *rules, end_idx, pad_idx)
         V = lp.shape[-1]
         cand = scores.unsqueeze(-1) + lp.view(B, K, V)
         only = torch.zeros_like(cand)
@@ -655,30 +786,37 @@ def _f32(x):
 
 
 def sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, n=1, temperature=1.0, top_k=0,
-                  top_p=1.0, seed=None, length_penalty=0.0, return_samples=False, incremental=None):
+                  top_p=1.0, seed=None, length_penalty=0.0, return_samples=False, incremental=None, no_repeat_ngram=0,
+                  min_len=0, repetition_penalty=1.0):
     """Sampled decoding with the reference decoder's arguments (rules above).  Returns tokens (B, m + 1) int64 (rule 7), then
     -- with return_samples -- all samples (B, n, m' + 1), their sum_logp (B, n) fp32 and the per-step model / sampling
     log-probs (B, n, m') fp32 (m': the steps of rule 6; zeros after a row's end).  seed=None draws one from `random`.
     incremental (default: on under the conditions beam_decode takes BeamDecoder, n <= 16) decodes through SampleDecoder;
-    otherwise every step re-runs model.inference over the (B*n)-row prefix batch in float64 (any model, CPU included)."""
+    otherwise every step re-runs model.inference over the (B*n)-row prefix batch in float64 (any model, CPU included).
+    no_repeat_ngram / min_len / repetition_penalty: the constraints section's rules; the draw and every returned log-prob
+    are then taken from the adjusted values, and a max_len + 1 above ops.LOGIT_RULES_MAX_HIST (256) takes the re-run path."""
     n, temperature, top_k, top_p = _sample_args(n, temperature, top_k, top_p)
+    rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty, max_len)
     seed = random.getrandbits(62) if seed is None else int(seed) % _U64
     with torch.no_grad():
         dec = _incremental(SampleDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, n, incremental,
-                           params=(temperature, top_k, top_p))
+                           params=(temperature, top_k, top_p), rules=rules)
         found = dec.run(seed) if dec is not None else _sample_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
-                                                                    modality, n, temperature, top_k, top_p, seed)
+                                                                    modality, n, temperature, top_k, top_p, seed, rules)
         return _sample_result(*found, end_idx, length_penalty, return_samples)
 
 
-def sample_decoder(n=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, length_penalty=0.0):
+def sample_decoder(n=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
+                   repetition_penalty=1.0):
     """a decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality), e.g.
     validation_1by1_loop(cfg, model, loader, sample_decoder(4, top_p=0.9), epoch, TBoard); seed=None: a fresh seed per call"""
     n, temperature, top_k, top_p = _sample_args(n, temperature, top_k, top_p)
+    rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty) or _NO_RULES
 
     def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
         return sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, n=n,
-                             temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, length_penalty=length_penalty)
+                             temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, length_penalty=length_penalty,
+                             no_repeat_ngram=rules[0], min_len=rules[1], repetition_penalty=rules[2])
     return decoder
 
 
@@ -715,9 +853,9 @@ def _sample_choose(lp, temperature, top_k, top_p, u):
     return torch.where(dead, arg, pick), torch.where(dead, zero, logq)
 
 
-def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, temperature, top_k, top_p, seed):
+def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, temperature, top_k, top_p, seed, rules=None):
     """rules 1-6 over full re-runs of model.inference on the (B*n)-row prefix batch -> (tokens (B, n, steps + 1),
-    sum_logp (B, n), step logp (B, n, steps), step logq (B, n, steps), steps)"""
+    sum_logp (B, n), step logp (B, n, steps), step logq (B, n, steps), steps); rules: what _rule_args returned"""
     import numpy as np
     B = fs['audio'].shape[0]
     dev = fs['audio'].device
@@ -730,7 +868,10 @@ def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, 
     rows = np.arange(R, dtype=np.uint64) << np.uint64(16)
     steps = 0
     while steps < max_len:
-        lp = _rerun_logp(model, x, rep, hist, modality, pad_idx).double()
+        lp = _rerun_logp(model, x, rep, hist, modality, pad_idx)
+        if rules is not None:
+            lp = _apply_rules(lp, hist, steps, *rules, end_idx, pad_idx)
+        lp = lp.double()
         u = torch.from_numpy(uniform01(seed, rows + np.uint64(steps))).to(dev)
         pick, logq = _sample_choose(lp, temperature, top_k, top_p, u)
         g = lp.gather(1, pick.unsqueeze(1)).squeeze(1)

@@ -829,3 +829,28 @@ def sample_step(logp, ld, rows, V, temperature, top_k, top_p, seed, seed_dev, t,
                                              finished.data_ptr(), tok.data_ptr(), out.data_ptr(), out.stride(0),
                                              sum_logp.data_ptr(), _p(step_logp), _p(step_logq), stream()),
                "bmhrl_sample_step")
+
+
+# ---- constrained caption decoding (csrc/constrain.hip)
+LOGIT_RULES_MAX_HIST = 256                    # BMHRL_LOGIT_RULES_MAX_HIST of include/bmhrl_hip.h
+
+
+def logit_rules(logp, ld, rows, V, hist, t, ngram, min_len, penalty, end_idx, pad_idx):
+    """repetition penalty, no-repeat n-gram ban and minimum length on every row of logp (rows, ld >= V) fp32, in place (see
+    bmhrl_logit_rules in include/bmhrl_hip.h): hist (rows, cols <= LOGIT_RULES_MAX_HIST) int64 holds the rows' sequences,
+    columns 0 .. t; t: (1,) int64 device word."""
+    _need_cuda(logp, hist, t)
+    if not (V >= 1 and ld >= V and rows >= 1 and logp.dtype == torch.float32 and logp.numel() >= (rows - 1) * ld + V):
+        raise ValueError("logit_rules: need V >= 1 and fp32 logp rows (rows, ld >= V)")
+    if not (ngram >= 0 and min_len >= 0 and math.isfinite(penalty) and penalty > 0):
+        raise ValueError("logit_rules: need ngram >= 0, min_len >= 0 and a finite penalty > 0")
+    if not (0 <= end_idx < V and 0 <= pad_idx < V):
+        raise ValueError("logit_rules: need 0 <= end_idx < V and 0 <= pad_idx < V")
+    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != rows or hist.stride(1) != 1 or \
+            not 1 <= hist.shape[1] <= LOGIT_RULES_MAX_HIST or hist.stride(0) != hist.shape[1]:
+        raise ValueError(f"logit_rules: hist must be a contiguous (rows, cols <= {LOGIT_RULES_MAX_HIST}) int64 buffer")
+    if t.dtype != torch.int64:
+        raise ValueError("logit_rules: t is an int64 word")
+    _lib.check(_lib.load().bmhrl_logit_rules(logp.data_ptr(), ld, rows, V, hist.data_ptr(), hist.stride(0), t.data_ptr(),
+                                             int(ngram), int(min_len), float(penalty), end_idx, pad_idx, stream()),
+               "bmhrl_logit_rules")

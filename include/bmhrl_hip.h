@@ -620,6 +620,26 @@ int bmhrl_sample_step(const float* logp, int64_t ld, int32_t rows, int32_t V, fl
                       int32_t pad_idx, uint8_t* finished, int64_t* tok, int64_t* out, int64_t ld_out, float* sum_logp,
                       float* step_logp, float* step_logq, bmhrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Constrained caption decoding (bmhrl_amd/decode.py; the rules are at the top of its constraints section).  For every row r
+ * of logp (rows, ld) fp32 log-probs, edited in place, with t read from the device word t[0] and the row's sequence
+ * s = hist[r][0 .. t] (int64 token ids, row stride ld_hist; ids outside [0, V) take part in the comparisons but select no
+ * entry):
+ *  1. penalty != 1: for every distinct id v of s with v != pad_idx, lp[v] = lp[v] * penalty (one fp32 multiply per id);
+ *  2. ngram = n >= 1 and t + 1 >= n: for every j in [0, t + 1 - n] with s[j .. j+n-2] == s[t-n+2 .. t],
+ *     lp[s[j+n-1]] = -inf (n = 1: every token of s);
+ *  3. t < min_len: lp[end_idx] = -inf;
+ *  in this order, so a banned entry is -inf whatever rule 1 did to it.  At most t + 2 entries of a row are written and
+ *  columns V .. ld-1 are never touched; ngram = 0, min_len = 0, penalty = 1 writes nothing.  The history holds ld_hist
+ *  positions per row, 1 <= ld_hist <= BMHRL_LOGIT_RULES_MAX_HIST (the kernel's LDS copy of s); a launch whose t lies
+ *  outside [0, ld_hist - 1] writes nothing.  rows >= 1, 1 <= V <= ld, ngram >= 0, min_len >= 0, penalty finite > 0,
+ *  0 <= end_idx < V, 0 <= pad_idx < V; other arguments are refused with -22.  Deterministic: no atomics.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_LOGIT_RULES_MAX_HIST 256
+int bmhrl_logit_rules(float* logp, int64_t ld, int32_t rows, int32_t V, const int64_t* hist, int64_t ld_hist,
+                      const int64_t* t, int32_t ngram, int32_t min_len, float penalty, int32_t end_idx, int32_t pad_idx,
+                      bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
