@@ -52,6 +52,7 @@ class GemmDesc(C.Structure):
 PROTOTYPES = {
     "bmhrl_gemm": [C.POINTER(GemmDesc), ptr],
     "bmhrl_gemm_group": [C.POINTER(GemmDesc), i32, ptr],
+    "bmhrl_gemm_f32_fast_path": [C.POINTER(GemmDesc)],
     "bmhrl_attention_fwd": [ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, i64, i64, i32, i32, i32, i32, i32, f32,
                             f32, u64, ptr, ptr],
     "bmhrl_attention_shared128_fwd": [ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, i64, i32, i32, i32, i32, f32, ptr],
@@ -153,7 +154,11 @@ def load() -> C.CDLL:
         C.CDLL(hip_rt, mode=C.RTLD_GLOBAL)
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in PROTOTYPES.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:      # (functions are added without a new ABI version: name the stale build, not just the symbol)
+            raise RuntimeError(f"{LIB_PATH} does not export {name}: it was built from older sources than this package; "
+                               "rebuild it with `python -m bmhrl_amd.build`") from None
         fn.argtypes = argtypes
         fn.restype = C.c_int
     lib.bmhrl_layernorm_bwd_workspace.argtypes = [i64, i32]

@@ -33,7 +33,7 @@ struct GemmArgs {
   const bf16_t* aux; long ldaux, aux_sb1, aux_sb2;
   float dropout_p; uint64_t seed; const uint64_t* seed_dev; long drop_sb1, drop_sb2, drop_sm;
   float* colsum; long cs_sb2, bias_sb2, cs_sb1, bias_sb1;
-  int tiles_m, splits, k_per_split, vec_ok, dbg, fast_bf16, fast_pd, tiles_mn;
+  int tiles_m, splits, k_per_split, vec_ok, dbg, fast_bf16, fast_pd, fast_f32, tiles_mn;
   int xcd_chunk, group_m;   // tile order of the direct-to-LDS kernel: see tile_of_block (0, 0: m fastest, the plain order)
   float* split_ws;          // ordered K split: the splits' partial tiles [batch][split][M][N] (summed by splitk_reduce_kernel)
 };
@@ -70,9 +70,17 @@ __device__ long long g_gemm_trace[2][8];
 #define BMHRL_GSTAMP(i)
 #endif
 
+// x * s as a product of its own: the compiler may not fuse it with a following addition.  Both fp32 epilogue loops scale a
+// dropped-out value with it before the residual is added, so their bit equality does not hang on how each happens to be compiled.
+__device__ __forceinline__ float f32_mul_unfused(float x, float s) {
+  float r = x * s;
+  asm volatile("" : "+v"(r));
+  return r;
+}
+
 // ---- epilogue, shared by the two main loops.  The accumulators (C/D layout: col = lane&31, row = (reg&3) + 8*(reg>>2) +
 // 4*(lane>>5)) go through LDS (`smem`: SMEM_ELEMS bf16 elements, free once every wave is past the main loop).
-template <int TM, int TN, int SMEM_ELEMS>
+template <int TM, int TN, int SMEM_ELEMS, bool F32_FAST = true>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[TM][TN], bf16_t* smem, const int b1, const int b2,
                                               const int m0, const int n0, const int split) {
   constexpr int BM = 64 * TM, BN = 64 * TN;
@@ -232,6 +240,88 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[T
     }
     return;
   }
+  // Fast path for the fp32-output LINEAR products (out-projection / second feed-forward GEMM with bias + dropout + residual, the
+  // dX and dW products, plain or accumulating): the generic loop below tests a dozen launch-uniform switches per 4-column piece
+  // and requests each piece's residual between the stores of the piece before.  Here the switches are template flags, the bias
+  // is requested once, and the residual / old C of ALL of a thread's pieces is requested before the accumulators are staged,
+  // so those loads fly while the tile goes through LDS.  Same staging image, same piece -> thread map (a wave covers whole
+  // rows of the tile: 512 B at BN = 128) and the same operations per element in the same order as the generic loop, so the
+  // two paths agree bit for bit (tests/test_gemm_f32_epilogue_gpu.py; BMHRL_GEMM_FAST_F32=0 forces the generic one).
+  // Interior tiles only: a tile that crosses the M or N edge takes the generic loop.  Instances (prepare() sets fast_f32 for
+  // exactly these; bias and alpha are run-time values, an absent bias adds 0 as in the generic loop):
+  //   plain | accumulate | residual | dropout + residual | dropout + residual + bf16 twin      (none with relu or column sums)
+  if constexpr (F32_FAST) {
+    if (p.fast_f32 && p.splits == 1 && m0 + BM <= p.M && n0 + BN <= p.N) {
+      constexpr int SC = BN + 4, CG = BN / 4, RS = 256 / CG, GROUPS = BM * BN / 4 / 256;
+      static_assert(BM * SC * 2 <= SMEM_ELEMS, "C tile must fit in the staging buffers");
+      float* sC = reinterpret_cast<float*>(smem);
+      const int row0 = tid / CG, c4 = (tid % CG) * 4;                  // piece i of this thread: row row0 + i * RS, columns c4 .. c4 + 3
+      const int m = m0 + row0, n = n0 + c4;
+      auto fast = [&](auto drop_, auto res_, auto acc_, auto twin_) {
+        constexpr bool DROP = decltype(drop_)::value, RES = decltype(res_)::value, ACC = decltype(acc_)::value,
+                       TWIN = decltype(twin_)::value;
+        float* __restrict__ dst = p.C + b1 * p.c_sb1 + b2 * p.c_sb2 + (long)m * p.ldc + n;
+        f32x4 b4 = {0.f, 0.f, 0.f, 0.f}, r4[GROUPS];
+        if (p.bias) b4 = *reinterpret_cast<const f32x4*>(p.bias + b1 * p.bias_sb1 + b2 * p.bias_sb2 + n);
+        if constexpr (RES) {
+          const float* __restrict__ src = p.residual + b1 * p.r_sb1 + b2 * p.r_sb2 + (long)m * p.ldr + n;
+#pragma unroll
+          for (int i = 0; i < GROUPS; ++i) r4[i] = *reinterpret_cast<const f32x4*>(src + (long)(i * RS) * p.ldr);
+        } else if constexpr (ACC) {
+#pragma unroll
+          for (int i = 0; i < GROUPS; ++i) r4[i] = *reinterpret_cast<const f32x4*>(dst + (long)(i * RS) * p.ldc);
+        }
+#pragma unroll
+        for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < TN; ++ni) {
+            float* base = sC + (wm * 32 * TM + mi * 32 + 4 * h) * SC + wn * 32 * TN + ni * 32 + r32;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) base[((r & 3) + 8 * (r >> 2)) * SC] = acc[mi][ni][r];
+          }
+        __syncthreads();
+        if (p.dbg == 5) return;                    // (tuning aid: staging only)
+        const uint64_t seed = p.seed + ((DROP && p.seed_dev) ? p.seed_dev[0] : 0ull);
+        const uint64_t id0 = (uint64_t)b1 * p.drop_sb1 + (uint64_t)b2 * p.drop_sb2;
+        // dropout_scale() of common.h with its threshold and its division done once (left to the compiler, the division lands
+        // in a divergent branch per element)
+        const uint32_t drop_thr = (uint32_t)fminf(p.dropout_p * 4294967296.f, 4294967040.f);
+        const float drop_keep = 1.0f / (1.0f - p.dropout_p);
+        bf16_t* __restrict__ dstb = TWIN ? p.Cb + b1 * p.cb_sb1 + b2 * p.cb_sb2 + (long)m * p.ldcb + n : nullptr;
+#pragma unroll
+        for (int i = 0; i < GROUPS; ++i) {
+          const f32x4 a4 = *reinterpret_cast<const f32x4*>(sC + (row0 + i * RS) * SC + c4);
+          f32x4 o;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float x = a4[j] * p.alpha + b4[j];
+            if constexpr (DROP) {
+              // (the product is rounded before the residual is added: f32_mul_unfused, as in the generic loop)
+              const uint32_t bits = dropout_bits(seed, id0 + (uint64_t)(m + i * RS) * p.drop_sm + (n + j));
+              x = f32_mul_unfused(x, bits < drop_thr ? 0.f : drop_keep);
+            }
+            o[j] = x + (RES ? r4[i][j] : 0.f);
+          }
+          if constexpr (ACC) o += r4[i];
+          if (p.dbg == 4) { if (o[0] == 123.25f) dst[0] = o[0]; continue; }           // (tuning aid: the epilogue without its stores)
+          *reinterpret_cast<f32x4*>(dst + (long)(i * RS) * p.ldc) = o;
+          if constexpr (TWIN) {
+            bf16x4 ob;
+            ob[0] = (bf16_t)o[0]; ob[1] = (bf16_t)o[1]; ob[2] = (bf16_t)o[2]; ob[3] = (bf16_t)o[3];
+            *reinterpret_cast<bf16x4*>(dstb + (long)(i * RS) * p.ldcb) = ob;
+          }
+        }
+      };
+      using T_ = std::true_type;
+      using F_ = std::false_type;
+      if (p.accumulate) fast(F_{}, F_{}, T_{}, F_{});
+      else if (!p.residual) fast(F_{}, F_{}, F_{}, F_{});
+      else if (p.dropout_p == 0.f) fast(F_{}, T_{}, F_{}, F_{});
+      else if (!p.Cb) fast(T_{}, T_{}, F_{}, F_{});
+      else fast(T_{}, T_{}, F_{}, T_{});
+      return;
+    }
+  }
   constexpr int SC = BN + 4;
   static_assert(BM * SC * 2 <= SMEM_ELEMS, "C tile must fit in the staging buffers");
   float* sC = reinterpret_cast<float*>(smem);
@@ -272,7 +362,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[T
       x = x * p.alpha + bias;
       if (!keep) x = NEG_MASK;
       if (p.relu) x = fmaxf(x, 0.f);
-      if (p.dropout_p > 0.f) x *= dropout_scale(p.dropout_p, seed, drop_base + (uint64_t)m * p.drop_sm + n);
+      if (p.dropout_p > 0.f) x = f32_mul_unfused(x, dropout_scale(p.dropout_p, seed, drop_base + (uint64_t)m * p.drop_sm + n));
       return x + res;
     } else if constexpr (KIND == 2) {
       x = x * p.alpha;
@@ -1106,7 +1196,7 @@ __global__ __launch_bounds__(512, 2) void gemm_glds8_kernel(const GemmArgs p) {
         for (int e = 0; e < 4; ++e) acc[mi][ni][4 * g + e] += v[e];
       }
   __syncthreads();                          // (the four remaining waves: the epilogue stages through the same memory)
-  gemm_epilogue<TM, TN, SMEM_ELEMS>(p, acc, smem, b1, b2, m0, n0, 0);
+  gemm_epilogue<TM, TN, SMEM_ELEMS, false>(p, acc, smem, b1, b2, m0, n0, 0);    // (generic fp32 epilogue: this kernel is off by default)
   BMHRL_GSTAMP(4)
 }
 
@@ -1123,7 +1213,7 @@ enum { LOOP_REG = 0, LOOP_GLDS = 1, LOOP_GLDS8 = 2 };
 enum { TILE_64 = 0, TILE_128 = 1, TILE_128x64 = 2 };
 enum { SPLIT_NONE = 0, SPLIT_ATOMIC = 1, SPLIT_ORDERED = 2 };
 enum { EPIPATH_FAST_BF16 = 0, EPIPATH_FAST_PD = 1, EPIPATH_GENERIC = 2 };
-struct GemmPlan { int loop, tile, stages, splits, split_form, epi_path, vec_ok, ordered_colsum; };
+struct GemmPlan { int loop, tile, stages, splits, split_form, epi_path, vec_ok, ordered_colsum, fast_f32; };
 
 template <int TM, int TN>
 hipError_t launch(const GemmArgs& a, const GemmPlan& pl, int a_trans, int b_trans, int batch, hipStream_t s) {
@@ -1347,6 +1437,13 @@ int prepare(const bmhrl_gemm_desc* d, GemmArgs& a, TilePlan& tp, int& batch) {
              al(d->bias, 16) && d->bias_sb2 % 4 == 0 && d->bias_sb1 % 4 == 0;
   a.fast_bf16 = d->Cb && !d->C && d->epilogue == BMHRL_EPI_LINEAR && !d->mask && !d->residual && !d->aux && !d->colsum &&
                 !d->accumulate && al(d->Cb, 16) && d->ldcb % 8 == 0 && d->cb_sb1 % 8 == 0 && d->cb_sb2 % 8 == 0;
+  // the specialised fp32 epilogue: LINEAR, no mask / aux / rowvec / relu / column sums, 16-byte accesses everywhere (a bf16 twin:
+  // 8-byte), and one of the instantiated combinations (gemm_epilogue lists them); BMHRL_GEMM_FAST_F32=0 forces the generic loop
+  static const int fast_f32_on = getenv("BMHRL_GEMM_FAST_F32") ? atoi(getenv("BMHRL_GEMM_FAST_F32")) : 1;     // (A/B runs, tests)
+  const bool f32_combo = d->accumulate ? (!d->residual && d->dropout_p == 0.f && !d->Cb)
+                                       : d->residual ? (d->dropout_p > 0.f || !d->Cb) : (d->dropout_p == 0.f && !d->Cb);
+  a.fast_f32 = fast_f32_on && d->C && d->epilogue == BMHRL_EPI_LINEAR && !d->mask && !d->aux && !d->rowvec && !d->rowvec2 &&
+               !d->relu && !d->colsum && f32_combo && a.vec_ok;
   const bool out_ok = d->Cb && !d->C && !d->residual && !d->colsum && !d->accumulate && !d->bias && al(d->Cb, 16) &&
                       d->ldcb % 8 == 0 && d->cb_sb1 % 8 == 0 && d->cb_sb2 % 8 == 0 && d->rowvec;
   a.fast_pd = (d->epilogue == BMHRL_EPI_PROB && out_ok && d->rowvec2 && (!d->mask || d->mask_sm == 0) && !d->aux) ||
@@ -1399,6 +1496,10 @@ int plan_problem(const bmhrl_gemm_desc* d, GemmArgs& a, GemmPlan& pl, int& batch
   pl.split_form = tp.splits == 1 ? SPLIT_NONE : a.split_ws ? SPLIT_ORDERED : SPLIT_ATOMIC;
   // (a K split's partial tiles leave through the generic epilogue's split branches)
   pl.epi_path = tp.splits == 1 && a.fast_bf16 ? EPIPATH_FAST_BF16 : tp.splits == 1 && a.fast_pd ? EPIPATH_FAST_PD : EPIPATH_GENERIC;
+  // the generic store path with its interior tiles served by the specialised fp32 loop (not in the eight-wave kernel; plan[5]
+  // stays "generic": bmhrl_gemm_f32_fast_path reports it)
+  if (tp.splits != 1 || pl.loop == LOOP_GLDS8) a.fast_f32 = 0;
+  pl.fast_f32 = a.fast_f32;
   pl.vec_ok = a.vec_ok;
   pl.ordered_colsum = bmhrl_deterministic() && a.colsum != nullptr;
   return 0;
@@ -1440,6 +1541,14 @@ extern "C" int bmhrl_gemm_plan(const bmhrl_gemm_desc* d, int32_t plan[8]) {
     plan[4] = pl.split_form; plan[5] = pl.epi_path; plan[6] = pl.vec_ok; plan[7] = pl.ordered_colsum;
   }
   return 0;
+}
+
+extern "C" int bmhrl_gemm_f32_fast_path(const bmhrl_gemm_desc* d) {
+  GemmArgs a;
+  GemmPlan pl;
+  int batch;
+  if (const int rc = plan_problem(d, a, pl, batch)) return rc;
+  return pl.fast_f32;
 }
 
 extern "C" int bmhrl_gemm_group_plan(const bmhrl_gemm_desc* d, int32_t n) {

@@ -116,6 +116,15 @@ def gemm_plan(d: "_lib.GemmDesc") -> dict:
     return dict(zip(GEMM_PLAN_FIELDS, plan))
 
 
+def gemm_f32_fast_path(d: "_lib.GemmDesc") -> bool:
+    """True when the interior tiles of d's fp32 output leave through the specialised fp32 epilogue (bmhrl_gemm_f32_fast_path;
+    gemm_plan reports such a launch as epi_path "generic"); raises for a descriptor bmhrl_gemm refuses"""
+    r = int(_lib.load().bmhrl_gemm_f32_fast_path(C.byref(d)))
+    if r < 0:
+        _lib.check(r, "bmhrl_gemm_f32_fast_path")
+    return bool(r)
+
+
 def gemm_group_plan(descs) -> int:
     """gemm_group_kernel launches bmhrl_gemm_group makes for these descriptors (0: one by one); raises on a refused one"""
     arr = (_lib.GemmDesc * len(descs))(*descs)

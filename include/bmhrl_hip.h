@@ -88,12 +88,20 @@ int bmhrl_gemm_splits(int32_t M, int32_t N, int32_t K, int32_t batch);
  *   plan[2] LDS stages    2 (register-staged: its two buffers), 2 or 4 (direct-to-LDS), 3 (8-wave)
  *   plan[3] K splits      1 = none
  *   plan[4] split form    0 none, 1 fp32 atomics into C, 2 ordered (partial tiles in split_ws + a reduction pass)
- *   plan[5] epilogue path 0 fast bf16, 1 fast softmax (PROB / DSCORE), 2 generic (also every K split's partial tiles)
+ *   plan[5] epilogue path 0 fast bf16, 1 fast softmax (PROB / DSCORE), 2 generic (also every K split's partial tiles; its
+ *                         interior tiles may take the specialised fp32 loop: bmhrl_gemm_f32_fast_path)
  *   plan[6] vec_ok        1: the generic path uses 16-byte accesses away from the right edge, 0: scalar accesses throughout
  *   plan[7] colsum pass   1: the column sums are a second, ordered pass (BMHRL_DETERMINISTIC=1), 0: atomics or none
  * Padding of the operands (columns K .. lda, or M / N .. lda when transposed) and gaps between batch entries may hold any
  * value, NaN included: no element outside the operands' logical extent reaches a stored output. */
 int bmhrl_gemm_plan(const bmhrl_gemm_desc* d, int32_t plan[8]);
+/* 1 when the interior tiles of *d's output leave through the specialised fp32 epilogue (plan[5] reports such a launch as
+ * generic: tiles on the M / N edge do take the generic loop, and the two agree bit for bit), 0 when every tile takes the path
+ * plan[5] names, < 0 for a refused descriptor.  It serves LINEAR products with an fp32 output, no K split, no mask / aux /
+ * row vectors / relu / column sums, every base and leading dimension aligned for vector accesses (plan[6]), in one of these
+ * forms: plain (+ bias), accumulate, (bias +) residual, (bias +) dropout + residual, the last also with a bf16 twin.
+ * BMHRL_GEMM_FAST_F32=0 in the environment (read once) turns it off.  Pure host function, as bmhrl_gemm_plan. */
+int bmhrl_gemm_f32_fast_path(const bmhrl_gemm_desc* d);
 /* bmhrl_gemm_group's decision for descs[0 .. n): the number of gemm_group_kernel launches it makes (per four problems: 1 when
  * they share one launch, 0 when they run one by one), < 0 for a refused descriptor. */
 int bmhrl_gemm_group_plan(const bmhrl_gemm_desc* descs, int32_t n);
