@@ -126,6 +126,7 @@ PROTOTYPES = {
     "bmhrl_adam_step_dev": [ptr, ptr, ptr, ptr, i64, f32, f32, f32, f32, f32, i32, ptr, f32, ptr, ptr],
     "bmhrl_adam_segments_dev": [ptr, i32, i32, ptr, ptr, ptr, ptr, f32, f32, f32, f32, f32, i32, ptr, f32, ptr, ptr],
     "bmhrl_grad_norm": [ptr, i32, i32, ptr, f32, ptr, i64, ptr, ptr],
+    "bmhrl_accum_segments": [ptr, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr],
     "bmhrl_beam_select": [ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, i32, ptr, ptr, i32, i32, i32, i32, i32, ptr],
     "bmhrl_beam_reorder": [ptr, i32, i64, ptr, i32, i32, ptr, i32, ptr],
     "bmhrl_rewards": [ptr, i64, ptr, i32, i64, ptr, i64, ptr, ptr, ptr, i32, i32, i32, f64, i32, i32, i32, ptr, i64, ptr, i64,

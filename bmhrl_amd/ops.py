@@ -594,6 +594,15 @@ def grad_norm(table, n_segments, n_blocks, grad, grad_scale, partials, hyper):
                                            partials.data_ptr(), partials.numel(), hyper.data_ptr(), stream()), "bmhrl_grad_norm")
 
 
+def accum_segments(table, n_segments, n_blocks, grad, accum, ctl, loss_in=None, loss_out=None):
+    """accum = w * g (ctl[1] != 0: the first micro-batch of a window, a store) or fma(w, g, accum), w = ctl[0], over the
+    gradient the Adam table describes (bmhrl_accum_segments in include/bmhrl_hip.h); ctl: two fp32 device words;
+    loss_in / loss_out: optional fp32 device scalars, loss_out = (first ? 0 : loss_out) + w * loss_in in the same launch"""
+    _need_cuda(table, grad, accum, ctl, loss_in, loss_out)
+    _lib.check(_lib.load().bmhrl_accum_segments(table.data_ptr(), n_segments, n_blocks, grad.data_ptr(), accum.data_ptr(),
+                                                ctl.data_ptr(), _p(loss_in), _p(loss_out), stream()), "bmhrl_accum_segments")
+
+
 def gemm_f32(A, W, bias1, bias2, C, M, N, K):
     _need_cuda(A, W, C)
     _lib.check(_lib.load().bmhrl_gemm_f32(A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), _p(bias1), _p(bias2),

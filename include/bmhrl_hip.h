@@ -515,6 +515,19 @@ int bmhrl_adam_segments(const int64_t* segments, int32_t n_segments, int32_t n_b
 int bmhrl_grad_norm(const int64_t* segments, int32_t n_segments, int32_t n_blocks, const float* grad, float grad_scale,
                     float* partials, int64_t partials_elems, float* hyper, bmhrl_stream_t stream);
 
+/* Gradient accumulation over a window of micro-batches (train.FlatAdam.accumulate), one launch per micro-batch over the
+ * gradient that `segments` describes -- the table of bmhrl_adam_segments: word 0 the offset, words 2 x 3 the element count,
+ * word 5 the first block, word 6 the gradient's address, 0 = grad + offset; words 1 and 4 are not read.
+ * ctl: two fp32 words in device memory, read by the kernel (a captured micro-step serves every micro-batch of a window):
+ *   ctl[0] = w, the weight of this micro-batch        ctl[1] != 0: the first micro-batch of a window
+ *   first:      accum[offset + i] = w * g[i]          (a store: accum is not read, a NaN or Inf left there does not survive)
+ *   otherwise:  accum[offset + i] = fma(w, g[i], accum[offset + i])
+ * Elementwise, no sum across threads: the same bits in every run.  The padding between one parameter's end and the next
+ * offset is never written.  loss_in / loss_out (optional, both or neither): loss_out[0] = (first ? 0 : loss_out[0]) +
+ * w * loss_in[0], formed by the same launch. */
+int bmhrl_accum_segments(const int64_t* segments, int32_t n_segments, int32_t n_blocks, const float* grad, float* accum,
+                         const float* ctl, const float* loss_in, float* loss_out, bmhrl_stream_t stream);
+
 /* bmhrl_adam_step / bmhrl_adam_segments with the learning rate and the clip coefficient read from the block: lr = hyper[0]
  * (the lr argument is not used) and the gradient is multiplied by the ONE fp32 factor grad_scale * hyper[2].  Bit-equal to
  * the entry point above called with that lr and that product as grad_scale. */
