@@ -133,6 +133,7 @@ PROTOTYPES = {
                       ptr],
     "bmhrl_sample_step": [ptr, i64, i32, i32, f32, i32, f32, u64, ptr, ptr, i64, i32, i32, ptr, ptr, ptr, i64, ptr, ptr, ptr, ptr],
     "bmhrl_logit_rules": [ptr, i64, i32, i32, ptr, i64, ptr, i32, i32, f32, i32, i32, ptr],
+    "bmhrl_consensus": [ptr, i64, i32, i32, i32, i64, i32, ptr, i32, ptr, ptr, ptr],
 }
 
 _lib = None

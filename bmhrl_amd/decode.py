@@ -16,6 +16,8 @@ sample_decode / sample_decoder: temperature / top-k / top-p sampling, n samples 
 (SampleDecoder), or over full re-runs.
 Every decoder takes no_repeat_ngram / min_len / repetition_penalty (the constraints section): the rules edit the step's
 log-probs before the choice, in the captured step through one HIP launch.
+beam_decode / sample_decode take select="consensus" (the consensus section): the returned caption is the hypothesis that
+agrees most with the clip's other hypotheses, one HIP launch after the token loop.
 """
 import math
 import random
@@ -553,7 +555,7 @@ def _apply_rules(lp, hist, t, ngram, min_len, penalty, end_idx, pad_idx):
 
 def beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, beam_size=4, length_penalty=0.0,
                 return_scores=False, return_beams=False, incremental=None, no_repeat_ngram=0, min_len=0,
-                repetition_penalty=1.0):
+                repetition_penalty=1.0, select="logp", consensus_n=4, consensus_weight=None):
     """Beam search with the reference decoder's arguments.  Returns tokens (B, n + 1) int64, then -- when asked -- the
     chosen hypotheses' raw scores (B,) fp32, then all K hypotheses sorted best first as tokens (B, K, m + 1) (m: the
     longest n_k of all of them, so that no hypothesis is cut) and raw scores (B, K).
@@ -561,30 +563,42 @@ def beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, mod
     through BeamDecoder; otherwise, or with incremental=False, every step re-runs model.inference over the (B*K)-row prefix
     batch (any model with `inference`, CPU included).  no_repeat_ngram / min_len / repetition_penalty: the constraints
     section's rules; the scores are then sums of adjusted log-probs, and a max_len + 1 above ops.LOGIT_RULES_MAX_HIST (256)
-    takes the re-run path."""
+    takes the re-run path.
+    select="consensus" (with consensus_n = N in [1, 4] and consensus_weight = None or a (V,) tensor of token weights)
+    replaces rule 5's choice by the consensus section's: the returned tokens and score are those of the hypothesis with the
+    largest utility, and return_beams appends the utilities (B, K) fp64 of the returned hypotheses, in their order, as the
+    LAST element of the tuple.  With select="logp" (the default) the tuple is as described above."""
     K = int(beam_size)
     if K < 1:
         raise ValueError(f"beam_size must be >= 1, got {beam_size}")
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty, max_len)
+    consensus = _consensus_args(select, consensus_n, consensus_weight)
     with torch.no_grad():
         dec = _incremental(BeamDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, K, incremental,
                            rules=rules)
         found = dec.run() if dec is not None else _beam_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
                                                               modality, K, rules)
-        return _beam_result(*found, end_idx, length_penalty, return_scores, return_beams)
+        if consensus is None:
+            return _beam_result(*found, end_idx, length_penalty, return_scores, return_beams)
+        util = _consensus_utilities(dec, found[0], found[2], end_idx, *consensus)
+        return _beam_result(*found, end_idx, length_penalty, return_scores, return_beams, util)
 
 
-def beam_decoder(beam_size=4, length_penalty=0.0, no_repeat_ngram=0, min_len=0, repetition_penalty=1.0):
+def beam_decoder(beam_size=4, length_penalty=0.0, no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, select="logp",
+                 consensus_n=4, consensus_weight=None):
     """a decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality), e.g.
-    validation_1by1_loop(cfg, model, loader, beam_decoder(4), epoch, TBoard)"""
+    validation_1by1_loop(cfg, model, loader, beam_decoder(4), epoch, TBoard); select / consensus_n / consensus_weight: the
+    consensus section's choice among the K beams"""
     if int(beam_size) < 1:
         raise ValueError(f"beam_size must be >= 1, got {beam_size}")
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty) or _NO_RULES
+    _consensus_args(select, consensus_n, consensus_weight)
 
     def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
         return beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, beam_size=beam_size,
                            length_penalty=length_penalty, no_repeat_ngram=rules[0], min_len=rules[1],
-                           repetition_penalty=rules[2])
+                           repetition_penalty=rules[2], select=select, consensus_n=consensus_n,
+                           consensus_weight=consensus_weight)
     return decoder
 
 
@@ -647,16 +661,23 @@ def _best_hypothesis(toks, scores, steps, end_idx, length_penalty):
     return n_k, order, toks[rows, order[:, 0], :n + 1].clone()
 
 
-def _beam_result(toks, scores, steps, end_idx, length_penalty, return_scores, return_beams):
-    """rules 5-6 over (B, K, >= steps + 1) hypotheses and their raw scores"""
+def _beam_result(toks, scores, steps, end_idx, length_penalty, return_scores, return_beams, util=None):
+    """rules 5-6 over (B, K, >= steps + 1) hypotheses and their raw scores; util: the hypotheses' consensus utilities (B, K),
+    in the rows' order -- the choice is then consensus rule R7 over rule 5's order"""
     toks = toks[..., :steps + 1]
     n_k, order, best = _best_hypothesis(toks, scores, steps, end_idx, length_penalty)
+    chosen = order[:, :1]
+    if util is not None:
+        pick, best = _consensus_choice(toks, n_k, order, util)
+        chosen = pick.unsqueeze(1)
     out = [best]
     if return_scores:
-        out.append(scores.gather(1, order[:, :1]).squeeze(1))
+        out.append(scores.gather(1, chosen).squeeze(1))
     if return_beams:
         m = int(n_k.max()) if scores.shape[0] else 0
         out += [toks.gather(1, order.unsqueeze(-1).expand(-1, -1, toks.shape[-1]))[..., :m + 1].clone(), scores.gather(1, order)]
+        if util is not None:
+            out.append(util.gather(1, order))
     return out[0] if len(out) == 1 else tuple(out)
 
 
@@ -787,36 +808,48 @@ def _f32(x):
 
 def sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, n=1, temperature=1.0, top_k=0,
                   top_p=1.0, seed=None, length_penalty=0.0, return_samples=False, incremental=None, no_repeat_ngram=0,
-                  min_len=0, repetition_penalty=1.0):
+                  min_len=0, repetition_penalty=1.0, select="logp", consensus_n=4, consensus_weight=None):
     """Sampled decoding with the reference decoder's arguments (rules above).  Returns tokens (B, m + 1) int64 (rule 7), then
     -- with return_samples -- all samples (B, n, m' + 1), their sum_logp (B, n) fp32 and the per-step model / sampling
     log-probs (B, n, m') fp32 (m': the steps of rule 6; zeros after a row's end).  seed=None draws one from `random`.
     incremental (default: on under the conditions beam_decode takes BeamDecoder, n <= 16) decodes through SampleDecoder;
     otherwise every step re-runs model.inference over the (B*n)-row prefix batch in float64 (any model, CPU included).
     no_repeat_ngram / min_len / repetition_penalty: the constraints section's rules; the draw and every returned log-prob
-    are then taken from the adjusted values, and a max_len + 1 above ops.LOGIT_RULES_MAX_HIST (256) takes the re-run path."""
+    are then taken from the adjusted values, and a max_len + 1 above ops.LOGIT_RULES_MAX_HIST (256) takes the re-run path.
+    select="consensus" (with consensus_n = N in [1, 4] and consensus_weight = None or a (V,) tensor of token weights)
+    replaces rule 7's choice by the consensus section's: the returned tokens are the sample with the largest utility, and
+    return_samples appends the samples' utilities (B, n) fp64, in the samples' order, as the LAST (sixth) element of the
+    tuple.  With select="logp" (the default) the tuple is as described above."""
     n, temperature, top_k, top_p = _sample_args(n, temperature, top_k, top_p)
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty, max_len)
+    consensus = _consensus_args(select, consensus_n, consensus_weight)
     seed = random.getrandbits(62) if seed is None else int(seed) % _U64
     with torch.no_grad():
         dec = _incremental(SampleDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, n, incremental,
                            params=(temperature, top_k, top_p), rules=rules)
         found = dec.run(seed) if dec is not None else _sample_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
                                                                     modality, n, temperature, top_k, top_p, seed, rules)
-        return _sample_result(*found, end_idx, length_penalty, return_samples)
+        if consensus is None:
+            return _sample_result(*found, end_idx, length_penalty, return_samples)
+        util = _consensus_utilities(dec, found[0], found[4], end_idx, *consensus)
+        return _sample_result(*found, end_idx, length_penalty, return_samples, util)
 
 
 def sample_decoder(n=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
-                   repetition_penalty=1.0):
+                   repetition_penalty=1.0, select="logp", consensus_n=4, consensus_weight=None):
     """a decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality), e.g.
-    validation_1by1_loop(cfg, model, loader, sample_decoder(4, top_p=0.9), epoch, TBoard); seed=None: a fresh seed per call"""
+    validation_1by1_loop(cfg, model, loader, sample_decoder(4, top_p=0.9), epoch, TBoard); seed=None: a fresh seed per call;
+    select / consensus_n / consensus_weight: the consensus section's choice among the n samples, e.g.
+    sample_decoder(8, top_p=0.9, select="consensus")"""
     n, temperature, top_k, top_p = _sample_args(n, temperature, top_k, top_p)
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty) or _NO_RULES
+    _consensus_args(select, consensus_n, consensus_weight)
 
     def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
         return sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, n=n,
                              temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, length_penalty=length_penalty,
-                             no_repeat_ngram=rules[0], min_len=rules[1], repetition_penalty=rules[2])
+                             no_repeat_ngram=rules[0], min_len=rules[1], repetition_penalty=rules[2], select=select,
+                             consensus_n=consensus_n, consensus_weight=consensus_weight)
     return decoder
 
 
@@ -889,13 +922,17 @@ def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, 
     return (hist.view(B, n, -1), sum_logp.float().view(B, n), f32(torch.stack(slp, 1)), f32(torch.stack(slq, 1)), steps)
 
 
-def _sample_result(toks, sum_logp, step_logp, step_logq, steps, end_idx, length_penalty, return_samples):
-    """rules 6-7 over (B, n, >= steps + 1) samples"""
+def _sample_result(toks, sum_logp, step_logp, step_logq, steps, end_idx, length_penalty, return_samples, util=None):
+    """rules 6-7 over (B, n, >= steps + 1) samples; util: the samples' consensus utilities (B, n) -- the choice is then
+    consensus rule R7 over rule 7's order"""
     toks = toks[..., :steps + 1]
-    out = _best_hypothesis(toks, sum_logp, steps, end_idx, length_penalty)[2]
+    n_k, order, out = _best_hypothesis(toks, sum_logp, steps, end_idx, length_penalty)
+    if util is not None:
+        out = _consensus_choice(toks, n_k, order, util)[1]
     if not return_samples:
         return out
-    return out, toks.clone(), sum_logp.clone(), step_logp[..., :steps].clone(), step_logq[..., :steps].clone()
+    found = (out, toks.clone(), sum_logp.clone(), step_logp[..., :steps].clone(), step_logq[..., :steps].clone())
+    return found if util is None else found + (util,)
 
 
 class SampleDecoder(IncrementalDecoder):
@@ -958,3 +995,140 @@ class SampleDecoder(IncrementalDecoder):
         B, n = self.B, self.K
         return (self.out[:, :m + 1].reshape(B, n, m + 1).clone(), self.sum_logp.view(B, n).clone(),
                 self.step_logp[:, :m].reshape(B, n, m).clone(), self.step_logq[:, :m].reshape(B, n, m).clone(), m)
+
+
+# ------------------------------------------------------------------------------------------------------------ consensus
+# Rules (both paths -- bmhrl_consensus after the incremental decoders' token loop, consensus_host after the re-runs --
+# implement exactly these).  select="consensus" keeps, per clip, the hypothesis that agrees most with the clip's other
+# hypotheses (minimum-Bayes-risk choice with an n-gram utility) instead of the one with the best length-normalised log-prob.
+# Inputs: the hypotheses of a clip toks (B, K, m + 1) int64, column 0 the start token; end_idx; the largest gram length
+# N in [1, 4] (consensus_n); optionally token_weight (V,) fp32 (consensus_weight).
+#  R1. words.  The words of hypothesis k are the tokens of columns 1 .. m before its first end_idx; the end token itself is
+#      not a word, and a hypothesis without one has all m tokens as words.  Every token before the end is a word whatever its
+#      id, pad_idx included.  l_k = the number of words, possibly 0;
+#  R2. grams and weights.  For g = 1 .. N the g-grams of k are its l_k - g + 1 runs of g consecutive words (none if l_k < g);
+#      c_k(y) = how often gram y occurs in k.  Without token_weight w(y) = 1.  With it, in fp64,
+#      w(y) = (w[y_0] + ... + w[y_{g-1}]) / g: the fp32 weights widened, added in token order, the division last.  A token
+#      id outside [0, V) weighs 0 and still compares by its id.  Weights are finite and >= 0 (the caller's contract);
+#  R3. gram mass.  W_k^g = sum of w(y) * c_k(y) over the distinct grams of k in the order of their first occurrence in k;
+#  R4. clipped match.  M_g(i, j) = sum of w(y) * min(c_i(y), c_j(y)) over the distinct grams of i in the order of their
+#      first occurrence in i;
+#  R5. pairwise utility.  u(i, j) = (t_1 + ... + t_N) / N with t_g = M_g(i, j) / max(W_i^g, W_j^g) when that maximum is > 0,
+#      else 0; the terms are added for g = 1 .. N in that order.  All arithmetic is fp64 without FMA contraction: one product,
+#      then one add;
+#  R6. utility.  U_i = (sum of u(i, j) over j != i, j ascending) / (K - 1); with K = 1, U_0 = 0.  Identical hypotheses vote
+#      separately (the Monte-Carlo estimate of the expected utility, intended).  Every row of the clip is a hypothesis, a
+#      beam that never came alive (score -inf: fewer candidates than beams) included;
+#  R7. the choice.  The clip's hypotheses are arranged in the order of sampling rule 7 / beam rule 5, best first; the largest
+#      U wins, ties to the earlier hypothesis of that order (a stable sort of -U over the arranged hypotheses).  The returned
+#      caption is cut and padded as without the keyword: (B, n + 1), n = max n_k of the chosen.
+# Without weights every product and sum of R3 / R4 is a small integer and u a sum of N quotients of integers; with weights the
+# prescribed order fixes every rounding: the device and the host compute the same IEEE operations, and their results are
+# compared for equality.  Refused with ValueError: a select other than "logp" / "consensus", consensus_n outside [1, 4] or no
+# integer, a consensus_weight that is no 1-D floating-point tensor with at least one entry.  With select="logp" (the default)
+# nothing of this section runs.
+
+
+def _consensus_args(select, consensus_n, consensus_weight):
+    """(N, weight) of valid arguments with select="consensus", None with select="logp" (the arguments are checked alike)"""
+    if select not in ("logp", "consensus"):
+        raise ValueError(f"select must be 'logp' or 'consensus', got {select!r}")
+    try:
+        whole = not isinstance(consensus_n, bool) and int(consensus_n) == consensus_n
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or not 1 <= int(consensus_n) <= ops.CONSENSUS_MAX_N:
+        raise ValueError(f"consensus_n must be an integer in [1, {ops.CONSENSUS_MAX_N}], got {consensus_n!r}")
+    w = consensus_weight
+    if w is not None and not (torch.is_tensor(w) and w.dim() == 1 and w.numel() >= 1 and w.is_floating_point()):
+        raise ValueError("consensus_weight must be None or a (V,) floating-point tensor of token weights")
+    return None if select == "logp" else (int(consensus_n), w)
+
+
+def _consensus_utilities(dec, toks, steps, end_idx, N, weight):
+    """R1-R6 -> U (B, K) fp64 on the hypotheses' device.  dec: the incremental decoder whose run() produced toks (its history
+    `out` still holds them: one bmhrl_consensus launch), None after a re-run (the host path; also for a history longer than
+    the kernel's ops.CONSENSUS_MAX_STEPS)."""
+    if dec is not None and steps <= ops.CONSENSUS_MAX_STEPS:
+        w = None if weight is None else weight.detach().to(device=dec.dev, dtype=torch.float32).contiguous()
+        return ops.consensus(dec.out, steps, dec.K, end_idx, N, w)
+    return consensus_host(toks[..., :steps + 1], end_idx, N, weight)
+
+
+def consensus_host(toks, end_idx, n=4, token_weight=None, pair=False):
+    """R1-R6 on the host for hypotheses toks (B, K, m + 1) int64 -> U (B, K) fp64 on toks' device [, with pair=True, the
+    pairwise utilities (B, K, K), u(i, i) = 0].  Python floats are IEEE doubles and `a + b * c` is one product, then one add,
+    so this is the arithmetic of the rules; the grams of a hypothesis are the keys of a dict, which keeps them in the order
+    of their first occurrence."""
+    t = toks.detach().cpu().tolist()
+    B, K = toks.shape[:2]
+    w32 = None if token_weight is None else [float(x) for x in token_weight.detach().to("cpu", torch.float32).tolist()]
+    V = 0 if w32 is None else len(w32)
+    util = [[0.0] * K for _ in range(B)]
+    pairs = [[[0.0] * K for _ in range(K)] for _ in range(B)]
+    for b in range(B):
+        words = []
+        for k in range(K):
+            row = t[b][k][1:]
+            words.append(row[:row.index(end_idx)] if end_idx in row else row)
+        u = pairs[b]
+        for g in range(1, n + 1):
+            weight, tables, mass = {}, [], []
+            for ws in words:
+                count = {}
+                for p in range(len(ws) - g + 1):
+                    gram = tuple(ws[p:p + g])
+                    count[gram] = count.get(gram, 0) + 1
+                    if gram not in weight:
+                        s = 1.0
+                        if w32 is not None:
+                            s = 0.0 + (w32[gram[0]] if 0 <= gram[0] < V else 0.0)
+                            for v in gram[1:]:
+                                s = s + (w32[v] if 0 <= v < V else 0.0)
+                            s = s / float(g)
+                        weight[gram] = s
+                W = 0.0
+                for gram, c in count.items():
+                    W = W + weight[gram] * float(c)
+                tables.append(count)
+                mass.append(W)
+            for i in range(K):
+                for j in range(K):
+                    if j == i:
+                        continue
+                    M = 0.0
+                    for gram, c in tables[i].items():
+                        M = M + weight[gram] * float(min(c, tables[j].get(gram, 0)))
+                    mx = max(mass[i], mass[j])
+                    u[i][j] = u[i][j] + (M / mx if mx > 0 else 0.0)
+        for i in range(K):
+            s = 0.0
+            for j in range(K):
+                if j != i:
+                    u[i][j] = u[i][j] / float(n)
+                    s = s + u[i][j]
+            util[b][i] = s / float(K - 1) if K > 1 else 0.0
+    U = torch.tensor(util, dtype=torch.float64, device=toks.device).view(B, K)
+    return (U, torch.tensor(pairs, dtype=torch.float64, device=toks.device).view(B, K, K)) if pair else U
+
+
+def _consensus_choice(toks, n_k, order, util):
+    """R7 over (B, K, >= n + 1) hypotheses, their n_k, their order (best first, of _best_hypothesis) and their utilities (B, K)
+    -> (the chosen hypotheses' indices (B,), their tokens (B, n + 1))"""
+    B = util.shape[0]
+    by_util = torch.sort(-util.gather(1, order), dim=1, stable=True).indices[:, :1]
+    pick = order.gather(1, by_util).squeeze(1)
+    rows = torch.arange(B, device=util.device)
+    n = int(n_k[rows, pick].max()) if B else 0
+    return pick, toks[rows, pick, :n + 1].clone()
+
+
+def idf_weights(counts, total=None):
+    """token weights for consensus_weight from a (V,) tensor of token counts (e.g. train_vocab.freqs in vocabulary order):
+    log(total / max(1, count)) computed in fp64, clamped at >= 0, as fp32; total=None: the sum of the counts.  Frequent
+    tokens (function words) weigh little, tokens never seen weigh log(total)."""
+    c = counts.detach().double()
+    total = float(c.sum()) if total is None else float(total)
+    if c.dim() != 1 or not total > 0:
+        raise ValueError("idf_weights: counts must be a (V,) tensor and total > 0")
+    return torch.log(total / c.clamp_min(1.0)).clamp_min(0.0).float()

@@ -13,7 +13,7 @@ import random
 
 import torch
 
-from ..decode import beam_decoder, greedy_decode, sample_decoder  # noqa: F401  (beam / sample decoders for the validation loops)
+from ..decode import beam_decoder, greedy_decode, idf_weights, sample_decoder  # noqa: F401  (beam / sample decoders for the validation loops; idf_weights: token weights of their select="consensus")
 from ..model.masking import make_masks
 
 

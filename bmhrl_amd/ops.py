@@ -872,3 +872,35 @@ def logit_rules(logp, ld, rows, V, hist, t, ngram, min_len, penalty, end_idx, pa
     _lib.check(_lib.load().bmhrl_logit_rules(logp.data_ptr(), ld, rows, V, hist.data_ptr(), hist.stride(0), t.data_ptr(),
                                              int(ngram), int(min_len), float(penalty), end_idx, pad_idx, stream()),
                "bmhrl_logit_rules")
+
+
+# ---- consensus choice among a clip's hypotheses (csrc/consensus.hip)
+CONSENSUS_MAX_STEPS = 256                     # BMHRL_CONSENSUS_MAX_STEPS of include/bmhrl_hip.h (K: BEAM_MAX)
+CONSENSUS_MAX_N = 4                           # BMHRL_CONSENSUS_MAX_N
+
+
+def consensus(hist, steps, K, end_idx, n=4, token_weight=None, pair=False):
+    """the consensus utilities util (B, K) fp64 of the hypotheses in hist (B * K, cols >= steps + 1) int64 -- a decoder's
+    token history: K consecutive rows per clip, column 0 the start token, columns 1 .. steps the generated tokens (see
+    bmhrl_consensus in include/bmhrl_hip.h).  n: the largest gram length; token_weight: None or (V,) fp32 on hist's device;
+    pair=True: also the pairwise utilities (B, K, K) fp64, u(i, i) written as 0."""
+    _need_cuda(hist, token_weight)
+    steps, K, n = int(steps), int(K), int(n)
+    if not (1 <= K <= BEAM_MAX and 0 <= steps <= CONSENSUS_MAX_STEPS and 1 <= n <= CONSENSUS_MAX_N):
+        raise ValueError(f"consensus: need 1 <= K <= {BEAM_MAX}, 0 <= steps <= {CONSENSUS_MAX_STEPS} and "
+                         f"1 <= n <= {CONSENSUS_MAX_N}")
+    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] < 1 or hist.shape[0] % K or hist.shape[1] < steps + 1 or \
+            hist.stride(1) != 1 or hist.stride(0) < steps + 1:
+        raise ValueError("consensus: hist must be (B * K, cols >= steps + 1) int64 with contiguous rows")
+    V = 0
+    if token_weight is not None:
+        V = token_weight.numel()
+        if token_weight.dtype != torch.float32 or token_weight.dim() != 1 or V < 1 or not token_weight.is_contiguous() or \
+                token_weight.device != hist.device:
+            raise ValueError("consensus: token_weight must be a contiguous (V >= 1,) fp32 tensor on hist's device")
+    B = hist.shape[0] // K
+    util = torch.empty(B, K, dtype=torch.float64, device=hist.device)
+    pairs = torch.empty(B, K, K, dtype=torch.float64, device=hist.device) if pair else None
+    _lib.check(_lib.load().bmhrl_consensus(hist.data_ptr(), hist.stride(0), B, K, steps, int(end_idx), n, _p(token_weight), V,
+                                           util.data_ptr(), _p(pairs), stream()), "bmhrl_consensus")
+    return (util, pairs) if pair else util

@@ -661,6 +661,25 @@ int bmhrl_logit_rules(float* logp, int64_t ld, int32_t rows, int32_t V, const in
                       const int64_t* t, int32_t ngram, int32_t min_len, float penalty, int32_t end_idx, int32_t pad_idx,
                       bmhrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Consensus (minimum-Bayes-risk) utilities of a clip's hypotheses (bmhrl_amd/decode.py; rules R1-R6 are at the top of its
+ * consensus section).  hist is a decoder's token history: row r = b * K + k holds hypothesis k of clip b, row stride ld,
+ * column 0 the start token and columns 1 .. steps the generated tokens; columns beyond `steps` are never read.  The words
+ * of a hypothesis are its tokens before the first end_idx (all `steps` tokens without one; an end_idx that is no token id
+ * never matches).  Writes util[b * K + i] = U_i, the mean over j != i of u(i, j) (0 with K = 1), and -- when pair is not
+ * null -- pair[(b * K + i) * K + j] = u(i, j), with u(i, i) written as 0.  u(i, j) is the mean over g = 1 .. N of the
+ * clipped g-gram match of i in j divided by the larger of the two gram masses, a gram weighing the mean of its tokens'
+ * token_weight[V] entries (null: every gram weighs 1; an id outside [0, V) weighs 0 and still compares by its id).  All
+ * arithmetic is fp64 in the order the rules prescribe, without FMA contraction and without atomics: equal inputs give
+ * equal bits.  B >= 1, 1 <= K <= BMHRL_CONSENSUS_MAX_K, 0 <= steps <= BMHRL_CONSENSUS_MAX_STEPS (0: every utility is 0),
+ * 1 <= N <= BMHRL_CONSENSUS_MAX_N, V >= 0 (>= 1 with token_weight), ld >= steps + 1; other arguments are refused with -22.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_CONSENSUS_MAX_K 16
+#define BMHRL_CONSENSUS_MAX_STEPS 256
+#define BMHRL_CONSENSUS_MAX_N 4
+int bmhrl_consensus(const int64_t* hist, int64_t ld, int32_t B, int32_t K, int32_t steps, int64_t end_idx, int32_t N,
+                    const float* token_weight, int32_t V, double* util, double* pair, bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
