@@ -814,6 +814,44 @@ def rewards(hyp, vmap, eos, ref, ref_len, df_keys, df_logs, metric, n, sigma, sc
                                          delta.stride(0), stream()), "bmhrl_rewards")
 
 
+# ---- per-prefix METEOR rewards (csrc/meteor.hip)
+def meteor(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, alpha, beta, gamma, scores, delta):
+    """per-prefix METEOR scores (B, L) fp64 and the first differences of their fp32 values (B, L) fp32 of the sampled
+    captions hyp (B, L) int64 against ref (>= B, R) int32 word ids, ref_len (>= B) int32; see bmhrl_meteor in
+    include/bmhrl_hip.h.  vstem (V) int32 with ref_stem shaped and strided like ref (both None: no stem stage); syn_off
+    (V + 1) int32 and syn_ids int32, at least one element (both None: no synonym stage)."""
+    _need_cuda(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, scores, delta)
+    B, L = hyp.shape
+    R = ref.shape[1]
+    V = vmap.numel()
+    if hyp.dtype != torch.int64 or vmap.dtype != torch.int32 or ref.dtype != torch.int32 or ref_len.dtype != torch.int32:
+        raise ValueError("meteor: hyp int64, vmap / ref / ref_len int32 expected")
+    if hyp.stride(1) != 1 or ref.stride(1) != 1 or not vmap.is_contiguous() or not ref_len.is_contiguous():
+        raise ValueError("meteor: hyp and ref need contiguous rows, vmap and ref_len contiguous")
+    if ref.shape[0] < B or ref_len.numel() < B:
+        raise ValueError("meteor: fewer reference rows than samples")
+    if (vstem is None) != (ref_stem is None):
+        raise ValueError("meteor: vstem and ref_stem go together")
+    if vstem is not None:
+        if vstem.dtype != torch.int32 or vstem.numel() != V or not vstem.is_contiguous():
+            raise ValueError("meteor: vstem (V) int32 expected")
+        if ref_stem.dtype != torch.int32 or ref_stem.shape != ref.shape or ref_stem.stride() != ref.stride():
+            raise ValueError("meteor: ref_stem int32, shaped and strided like ref, expected")
+    n_syn = 0
+    if syn_off is not None and syn_ids is not None:
+        n_syn = syn_ids.numel()
+        if syn_off.dtype != torch.int32 or syn_ids.dtype != torch.int32 or syn_off.numel() != V + 1 or n_syn < 1 or \
+                not syn_off.is_contiguous() or not syn_ids.is_contiguous():
+            raise ValueError("meteor: syn_off (V + 1) int32 and syn_ids (>= 1) int32 expected")
+    if scores.dtype != torch.float64 or delta.dtype != torch.float32 or tuple(scores.shape) != (B, L) or \
+            tuple(delta.shape) != (B, L) or scores.stride(1) != 1 or delta.stride(1) != 1:
+        raise ValueError("meteor: scores (B, L) fp64 and delta (B, L) fp32 with contiguous rows expected")
+    _lib.check(_lib.load().bmhrl_meteor(hyp.data_ptr(), hyp.stride(0), vmap.data_ptr(), _p(vstem), V, _p(syn_off), _p(syn_ids),
+                                        n_syn, ref.data_ptr(), _p(ref_stem), ref.stride(0), ref_len.data_ptr(), float(alpha),
+                                        float(beta), float(gamma), B, L, R, scores.data_ptr(), scores.stride(0),
+                                        delta.data_ptr(), delta.stride(0), stream()), "bmhrl_meteor")
+
+
 # ---- sampled caption decoding (csrc/sample.hip)
 SAMPLE_MAX_V = 16384                          # BMHRL_SAMPLE_MAX_V of include/bmhrl_hip.h
 

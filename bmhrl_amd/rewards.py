@@ -14,7 +14,12 @@ Graph-safe use: scorer.bind(captions) copies the batch's reference word ids into
 host -> device copy, no read-back); CaptionTrainer(phase="worker", reward_fn=scorer.reward_fn()) captures the reward
 launch in the step graph, and bind(batch["captions"]) before each replay() refreshes it.
 
-install() registers metrics.cider and metrics.bleu in sys.modules so that the reference's driver imports these classes.
+METEOR (MeteorScorer, csrc/meteor.hip, bmhrl_meteor): stemming and synonym lookup depend on the
+vocabulary alone, so they become tables built here once (MeteorTables: vocab id -> stem id, and the synonym sets as CSR rows
+of word ids); the reference buffer then carries a row of stem ids beside the row of word ids.
+
+install() registers metrics.cider and metrics.bleu in sys.modules so that the reference's driver imports these classes;
+install(meteor=True) also metrics.batched_meteor.
 """
 from __future__ import annotations
 
@@ -74,6 +79,18 @@ def vocab_word_ids(itos: Sequence[str], table: StringTable, lower: bool) -> np.n
         if words:
             out[i] = table[words[0]]
     return out
+
+
+def vocab_strings(itos: Sequence[str]) -> StringTable:
+    """the string table of a vocabulary: every entry, raw and lowercased, then the words the vocab maps point at"""
+    table = StringTable()
+    for s in itos:
+        table.add(s)
+        table.add(s.lower())
+    for s in itos:
+        for w in s.split() + s.lower().split():
+            table.add(w)
+    return table
 
 
 class DocFrequency:
@@ -162,13 +179,7 @@ class _DeviceScorer:
         self.gamma = gamma
         self.gamma_m = gamma_manager
         itos = list(vocab.itos)
-        self.strings = StringTable()
-        for s in itos:
-            self.strings.add(s)
-            self.strings.add(s.lower())
-        for s in itos:                        # the words the maps point at
-            for w in s.split() + s.lower().split():
-                self.strings.add(w)
+        self.strings = vocab_strings(itos)
         self.df = DocFrequency(dictionary, self.strings) if dictionary is not None else None
         cider = self.metric == ops.REWARD_CIDER
         vmap = vocab_word_ids(itos, self.strings, lower=not cider)
@@ -182,7 +193,7 @@ class _DeviceScorer:
             self.df_logs = torch.from_numpy(self.df.logs).to(self.device)
         else:
             self.df_keys = self.df_logs = None
-        self._ref = None                      # (capacity rows, R) int32 device words, then capacity ref_len words
+        self._ref = None                      # encode()'s planes of (capacity rows, R) int32 ids, then capacity ref_len words
         self._ref_host = None
         self._copied = None                   # event of the last host -> device copy out of _ref_host
         self._bound = 0
@@ -204,32 +215,42 @@ class _DeviceScorer:
             out.append(ids)
         return out
 
+    def encode(self, captions: Sequence[str]) -> List[List[List[int]]]:
+        """the id rows a caption puts into the reference buffer, plane by plane (here one plane: the word ids)"""
+        return [self.tokenize(captions)]
+
     def bind(self, captions: Sequence[str]) -> None:
         """tokenize the batch's reference captions and copy their word ids into the fixed device buffer (one non-blocking
         copy on the current stream, no read-back).  The buffer keeps its address while the batch size does not grow, so a
         captured reward launch reads the newly bound captions at its next replay."""
-        ids = self.tokenize(captions)
-        B, R = len(ids), ops.REWARDS_MAX_R
+        planes = self.encode(captions)
+        P, B, R = len(planes), len(planes[0]), ops.REWARDS_MAX_R
         if B == 0:
             raise ValueError("bind: no captions")
         if self._ref is None or self._ref_rows < B:
             self._ref_rows = B
-            self._ref = torch.empty(B * R + B, dtype=torch.int32, device=self.device)
-            self._ref_host = torch.empty(B * R + B, dtype=torch.int32, pin_memory=True)
+            self._ref = torch.empty(P * B * R + B, dtype=torch.int32, device=self.device)
+            self._ref_host = torch.empty(P * B * R + B, dtype=torch.int32, pin_memory=True)
             self._copied = None
         if self._copied is not None:
             self._copied.synchronize()        # the previous copy out of the staging buffer has finished
         rows = self._ref_rows
         host = self._ref_host.numpy()
-        words, lens = host[:rows * R].reshape(rows, R), host[rows * R:]
+        words, lens = host[:P * rows * R].reshape(P, rows, R), host[P * rows * R:]
         lens[:] = 0
-        for b, w in enumerate(ids):
-            words[b, :len(w)] = w
-            lens[b] = len(w)
+        for p, ids in enumerate(planes):
+            for b, w in enumerate(ids):
+                words[p, b, :len(w)] = w
+                lens[b] = len(w)
         self._ref.copy_(self._ref_host, non_blocking=True)
         self._copied = torch.cuda.Event()
         self._copied.record()
         self._bound = B
+
+    def bound(self) -> Tuple[Tensor, Tensor]:
+        """views of the device buffer: ref (planes, capacity rows, R) int32 ids and ref_len (capacity rows) int32"""
+        rows, R = self._ref_rows, ops.REWARDS_MAX_R
+        return self._ref[:-rows].view(-1, rows, R), self._ref[-rows:]
 
     def _launch(self, pred: Tensor) -> Tuple[Tensor, Tensor]:
         """(delta (B, L) fp32, scores (B, L) fp64) of the sampled tokens against the bound captions"""
@@ -239,13 +260,16 @@ class _DeviceScorer:
         if L > ops.REWARDS_MAX_L:
             raise ValueError(f"captions of {L} tokens; at most {ops.REWARDS_MAX_L} are supported")
         hyp = pred if (pred.dtype == torch.int64 and pred.stride(1) == 1) else pred.long().contiguous()
-        rows, R = self._ref_rows, ops.REWARDS_MAX_R
-        ref, ref_len = self._ref[:rows * R].view(rows, R), self._ref[rows * R:]
+        ref, ref_len = self.bound()
         scores = torch.empty(B, L, dtype=torch.float64, device=self.device)
         delta = torch.empty(B, L, dtype=torch.float32, device=self.device)
-        ops.rewards(hyp, self.vmap, self.eos, ref, ref_len, self.df_keys, self.df_logs, self.metric, self._n, self._sigma,
-                    scores, delta)
+        self._score(hyp, ref, ref_len, scores, delta)
         return delta, scores
+
+    def _score(self, hyp, ref, ref_len, scores, delta):
+        """the launch: ref (planes, rows, R) as encode() laid it out"""
+        ops.rewards(hyp, self.vmap, self.eos, ref[0], ref_len, self.df_keys, self.df_logs, self.metric, self._n, self._sigma,
+                    scores, delta)
 
     def _diff(self, pred, target):
         if target is not None:
@@ -344,6 +368,148 @@ class BleuScorer(_DeviceScorer):
         return rl_glue.discontinue_reward(bleu_diff, gamma), rewards
 
 
+def _nltk_stemmer():
+    from nltk.stem.porter import PorterStemmer
+    return PorterStemmer()
+
+
+def _nltk_synonyms():
+    from nltk.corpus import wordnet
+
+    def synonyms(word):
+        """the lemma names without "_" of every synset of the word, as nltk's _enum_wordnetsyn_match collects them"""
+        return [lemma.name() for synset in wordnet.synsets(word) for lemma in synset.lemmas() if lemma.name().find("_") < 0]
+    return synonyms
+
+
+class MeteorTables:
+    """the host side of the METEOR scorer: what stemming and synonym lookup contribute, as tables over the vocabulary.
+    strings / stems: the word and stem string tables; vmap (V,) int32 vocab id -> id of the entry's lowercased word (-1: no
+    word); vstem (V,) int32 vocab id -> id of that word's stem (-1: no word; None: no stem stage); syn_off (V + 1,) /
+    syn_ids int32: per vocab id the ascending, distinct word ids of synonyms(word) (None: no synonym stage).  A row holds
+    the word itself only when `synonyms` returns it; the kernel counts the word itself as its own synonym either way.
+    Every synonym is added to the word table, so a reference word that is one gets the same id.  syn_ids is never empty
+    (one -1 stands in), so its device pointer is never null.
+
+    stemmer: an object with .stem(str) -> str (None: nltk's PorterStemmer, False: no stem stage); synonyms: a callable
+    word -> iterable of str (None: the WordNet lemma names, False: no synonym stage)."""
+
+    def __init__(self, itos: Sequence[str], stemmer=None, synonyms=None, strings: StringTable = None):
+        if stemmer is None or synonyms is None:
+            try:
+                stemmer = _nltk_stemmer() if stemmer is None else stemmer
+                synonyms = _nltk_synonyms() if synonyms is None else synonyms
+            except ImportError as e:
+                raise ImportError("METEOR's default stemmer and synonyms come from nltk (PorterStemmer, WordNet), which cannot "
+                                  "be imported; install it, or pass stemmer= (an object with .stem) and synonyms= (a callable "
+                                  "word -> words); False switches the stage off") from e
+        itos = list(itos)
+        self.strings = strings if strings is not None else vocab_strings(itos)
+        self.vmap = vocab_word_ids(itos, self.strings, lower=True)
+        self._stem = stemmer.stem if stemmer is not False else None
+        self._stem_cache: Dict[str, str] = {}
+        self.stems = StringTable()
+        words = [s.lower().split() for s in itos]
+        self.vstem = None
+        if self._stem is not None:
+            self.vstem = np.full(len(itos), -1, dtype=np.int32)
+            for i, w in enumerate(words):
+                if w:
+                    self.vstem[i] = self.stems.add(self.stem(w[0]))
+        self.syn_off = self.syn_ids = None
+        if synonyms is not False:
+            rows = [sorted({self.strings.add(str(x)) for x in synonyms(w[0])}) if w else [] for w in words]
+            self.syn_off = np.zeros(len(itos) + 1, dtype=np.int32)
+            self.syn_off[1:] = np.cumsum([len(r) for r in rows])
+            flat = [i for r in rows for i in r]
+            self.syn_ids = np.asarray(flat if flat else [-1], dtype=np.int32)
+
+    def stem(self, word: str) -> str:
+        s = self._stem_cache.get(word)
+        if s is None:
+            s = self._stem_cache[word] = self._stem(word)
+        return s
+
+    def encode(self, captions: Sequence[str]) -> List[List[List[int]]]:
+        """[word ids, stem ids] of every caption's lowercased, whitespace-split words; words and stems outside the tables
+        get fresh ids (this batch).  Without a stem stage the stem ids are -1."""
+        fresh_w: Dict[str, int] = {}
+        fresh_s: Dict[str, int] = {}
+        out_w, out_s = [], []
+        for c in captions:
+            ws, ss = [], []
+            for w in c.lower().split():
+                i = self.strings.get(w)
+                if i is None:
+                    i = fresh_w.setdefault(w, len(self.strings) + len(fresh_w))
+                ws.append(i)
+                j = -1
+                if self._stem is not None:
+                    s = self.stem(w)
+                    j = self.stems.get(s)
+                    if j is None:
+                        j = fresh_s.setdefault(s, len(self.stems) + len(fresh_s))
+                ss.append(j)
+            if len(ws) > ops.REWARDS_MAX_R:
+                raise ValueError(f"reference caption of {len(ws)} words; at most {ops.REWARDS_MAX_R} are supported")
+            out_w.append(ws)
+            out_s.append(ss)
+        return [out_w, out_s]
+
+
+class MeteorScorer(_DeviceScorer):
+    """metrics/batched_meteor.py MeteorScorer on the device (its constructor arguments, .type, methods and results; the
+    rules are in DESIGN.md section 19).  stemmer / synonyms: see MeteorTables."""
+    type = "METEOR"
+    alpha, beta, gamma_frag = 0.9, 3.0, 0.5       # single_meteor_score's defaults, which the reference uses
+
+    def __init__(self, vocab, device, gamma_step, gamma_section, stemmer=None, synonyms=None):
+        super().__init__(vocab, device, gamma_step, gamma_section, 4, 6.0)
+        self.gamma_manager = gamma_section
+        self.tables = MeteorTables(vocab.itos, stemmer, synonyms, strings=self.strings)
+        dev = lambda a: None if a is None else torch.from_numpy(a).to(self.device)                       # noqa: E731
+        self.vstem, self.syn_off, self.syn_ids = dev(self.tables.vstem), dev(self.tables.syn_off), dev(self.tables.syn_ids)
+
+    def encode(self, captions):
+        return self.tables.encode(captions)
+
+    def _score(self, hyp, ref, ref_len, scores, delta):
+        ops.meteor(hyp, self.vmap, self.vstem, self.syn_off, self.syn_ids, ref[0], ref[1] if self.vstem is not None else None,
+                   ref_len, self.alpha, self.beta, self.gamma_frag, scores, delta)
+
+    def _meteor_diff(self, pred, trg, mask=None):
+        delta, scores = self._diff(pred, trg)
+        return delta, scores.float()
+
+    def delta_meteor_segment(self, delta_meteor_step_reward, sections, gamma):
+        segment_meteor_dif, segment_reward_index = rl_glue.segment_reward(delta_meteor_step_reward, sections)
+        return rl_glue.discontinue_reward(segment_meteor_dif, gamma), segment_reward_index
+
+    def delta_meteor_step(self, pred, trg, mask, gamma):
+        meteor_diff, rewards = self._meteor_diff(pred, trg, mask)
+        return rl_glue.discontinue_reward(meteor_diff, gamma), rewards
+
+    def delta_meteor_worker(self, pred, trg, mask=None):
+        delta_meteor_step_reward, rewards = self.delta_meteor_step(pred, trg, mask, self.gamma)
+        return delta_meteor_step_reward.float(), rewards
+
+    def delta_meteor_manager(self, pred, trg, mask, sections):
+        manager_segment_score, _ = self.delta_meteor(pred, trg, mask, sections)
+        return manager_segment_score.float(), None
+
+    def delta_meteor(self, pred, trg, mask, sections):
+        delta_meteor_step_reward, rewards = self.delta_meteor_step(pred, trg, mask, self.gamma)
+        delta_meteor_section_reward, _ = self.delta_meteor_segment(delta_meteor_step_reward, sections, self.gamma)
+        return delta_meteor_section_reward, rewards
+
+    def get_meteor_gamma(self, gamma, B, L):
+        """(B, L, L): row i holds gamma^(k - i) at columns k >= i, zeros before"""
+        return rl_glue.discount_matrix(L, gamma, n_step=L, device=self.device).expand(B, L, L).contiguous()
+
+
+segment_reward = rl_glue.segment_reward       # metrics/batched_meteor.py exposes it (tests/golden/make_golden.py reads it there)
+
+
 def _mark_caption_ends(sections: Tensor, trg: Sequence[str], B: int) -> None:
     """delta_cider_manager's in-place write: sections[i][e] = 1 and sections[i][e + 1:] = 0 with e = len(trg[i].split()),
     row by row; the row whose e is not a valid index raises IndexError after the rows before it were written"""
@@ -360,9 +526,10 @@ def _mark_caption_ends(sections: Tensor, trg: Sequence[str], B: int) -> None:
         raise IndexError(f"index {ends[bad]} is out of bounds for dimension 0 with size {L}")
 
 
-def install() -> List[str]:
+def install(meteor: bool = False) -> List[str]:
     """register metrics.cider and metrics.bleu (the reference's scorer modules) as this module, so that the driver's
-    `from metrics.cider import CiderScorer` gets the device scorers.  Opt-in; bmhrl_amd.install does not do it."""
+    `from metrics.cider import CiderScorer` gets the device scorers; meteor=True registers metrics.batched_meteor too
+    (MeteorScorer, segment_reward).  Opt-in; bmhrl_amd.install does not do it."""
     if "metrics" not in sys.modules:
         try:
             importlib.import_module("metrics")           # the reference's package, when it is on sys.path
@@ -370,7 +537,7 @@ def install() -> List[str]:
             sys.modules["metrics"] = types.ModuleType("metrics")
             sys.modules["metrics"].__path__ = []
     mod = sys.modules[__name__]
-    names = ["metrics.cider", "metrics.bleu"]
+    names = ["metrics.cider", "metrics.bleu"] + (["metrics.batched_meteor"] if meteor else [])
     for name in names:
         sys.modules[name] = mod
         setattr(sys.modules["metrics"], name.split(".")[1], mod)

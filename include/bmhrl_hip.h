@@ -622,6 +622,28 @@ int bmhrl_rewards(const int64_t* hyp, int64_t ldh, const int32_t* vmap, int32_t 
                   float* delta, int64_t ldd, bmhrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-prefix METEOR rewards (bmhrl_amd/rewards.py MeteorScorer; the rules are in DESIGN.md section 19): nltk's
+ * single_meteor_score of every prefix of every sampled caption against its reference caption, as the reference's
+ * metrics/batched_meteor.py computes it on the host.  No cut at an end token.
+ *  hyp (B, L) int64 vocab ids, row stride ldh; vmap[V]: vocab id -> word id (-1: the token yields no word and its position
+ *  repeats the score before it; ids outside [0, V) yield none either); vstem[V]: vocab id -> stem id of the entries that
+ *  yield a word (null: no stem stage); syn_off[V + 1], syn_ids[n_syn]: the synonym sets of the entries' words as CSR rows
+ *  of word ids (both null: no synonym stage; exactly one null is refused; offsets are clamped to [0, n_syn]; the word
+ *  itself always belongs to its set, listed or not).  ref / ref_stem (B, R) int32 word ids / stem ids of the reference
+ *  words, one row stride ldr, of which ref_len[b] (device, clamped to [0, R]) are used; ref_stem is read only with vstem.
+ *  Every prefix is aligned from scratch: exact, then stem, then synonym matches, each over what the stage before left
+ *  unmatched, hypothesis words from last to first, each taking the highest unmatched reference position that passes.
+ *  score = (1 - gamma * pow(chunks / m, beta)) * P R / (alpha P + (1 - alpha) R) in fp64; 0 without a match.
+ *  Writes scores (B, L) fp64 and delta (B, L) fp32 (column 0: the score as fp32, then differences of the fp32 scores).
+ *  L <= BMHRL_REWARDS_MAX_L, R <= BMHRL_REWARDS_MAX_R; other shapes and null required pointers are refused with -22.
+ *  Deterministic: no atomics, no reduction across samples.
+ * ------------------------------------------------------------------------------------------- */
+int bmhrl_meteor(const int64_t* hyp, int64_t ldh, const int32_t* vmap, const int32_t* vstem, int32_t V,
+                 const int32_t* syn_off, const int32_t* syn_ids, int32_t n_syn, const int32_t* ref, const int32_t* ref_stem,
+                 int64_t ldr, const int32_t* ref_len, double alpha, double beta, double gamma, int32_t B, int32_t L,
+                 int32_t R, double* scores, int64_t lds, float* delta, int64_t ldd, bmhrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sampled caption decoding (bmhrl_amd/decode.py SampleDecoder; the rules are at the top of its sampling section).  One step
  * for every row r of logp (rows, ld) fp32 log-probs, t read from the device word t[0]:
  *  finished[r] != 0: tok[r] = pad_idx, out[r][t + 1] = pad_idx, step_logp / step_logq [r][t] = 0, sum_logp unchanged;
