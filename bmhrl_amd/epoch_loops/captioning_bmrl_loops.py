@@ -14,6 +14,7 @@ import random
 import torch
 
 from ..decode import beam_decoder, greedy_decode, idf_weights, sample_decoder  # noqa: F401  (beam / sample decoders for the validation loops; idf_weights: token weights of their select="consensus")
+from ..loss.hungarian_matcher import loss_labels  # noqa: F401  (the DETR word loss, defined here in the reference: :1114-1129)
 from ..model.masking import make_masks
 
 

@@ -2159,3 +2159,37 @@ class ReinforceFn(torch.autograd.Function):
         ops.reinforce_bwd(probs, V, a, v, c, dloss.reshape(1).float().contiguous(), dprobs, dv, dc, rows, V)
         return (dprobs if need[0] else None), None, (dv.view(vshape) if dv is not None else None), \
             (dc.view(cshape) if dc is not None else None)
+
+
+def _logit_rows(logits):
+    """logits (B, Q, C) as the word-loss kernels take them: fp32, unit column stride, one row stride (else a copy)"""
+    x = logits if logits.dtype == torch.float32 else logits.float()
+    B, Q, Cn = x.shape
+    ld = x.stride(1) if Q > 1 else (x.stride(0) if B > 1 else Cn)
+    ok = (Cn == 1 or x.stride(2) == 1) and ld >= Cn and (Q == 1 or B == 1 or x.stride(0) == Q * ld)
+    return x if ok else x.contiguous()
+
+
+class DetrWordLossFn(torch.autograd.Function):
+    """The DETR word loss (loss/hungarian_matcher.py:42-59 + captioning_bmrl_loops.py:1114-1129): the caption's words
+    (entries != pad_idx, ids outside [0, C - 2] dropped) are matched one to one to the Q queries by minimum total
+    -cost_scale * softmax(logits)[q, word], and the (B, Q, C) logits are scored by the cross entropy with weight eos_coef on
+    the rows of the unmatched queries, whose class is C - 1.  query_of_target (B, L) int32 on the device, when given,
+    replaces the matching.  Four launches (csrc/word_loss.hip), no host synchronisation in either direction."""
+
+    @staticmethod
+    def forward(ctx, logits, captions, pad_idx, eos_coef, cost_scale, query_of_target=None):
+        x = _logit_rows(logits.detach())
+        cap = captions if captions.stride(-1) == 1 or captions.shape[-1] == 1 else captions.contiguous()
+        words, n_words, lse, x_none, gathered, cost = ops.word_cost(x, cap, pad_idx, cost_scale)
+        qot = ops.lsa_match(cost, n_words) if query_of_target is None else query_of_target.to(torch.int32).contiguous()
+        tgt_class, row_w, loss_scale = ops.word_loss(words, n_words, qot, lse, x_none, gathered, eos_coef, x.shape[2])
+        ctx.save_for_backward(x, lse, tgt_class, row_w, loss_scale)
+        ctx.in_dtype = logits.dtype
+        return loss_scale[0].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        x, lse, tgt_class, row_w, loss_scale = ctx.saved_tensors
+        g = ops.word_loss_bwd(x, lse, tgt_class, row_w, loss_scale, dloss.reshape(1).float().contiguous())
+        return (g if ctx.in_dtype == torch.float32 else g.to(ctx.in_dtype)), None, None, None, None, None

@@ -942,3 +942,111 @@ def consensus(hist, steps, K, end_idx, n=4, token_weight=None, pair=False):
     _lib.check(_lib.load().bmhrl_consensus(hist.data_ptr(), hist.stride(0), B, K, steps, int(end_idx), n, _p(token_weight), V,
                                            util.data_ptr(), _p(pairs), stream()), "bmhrl_consensus")
     return (util, pairs) if pair else util
+
+
+# ---- DETR word loss: Hungarian matching + weighted cross entropy (csrc/word_loss.hip)
+WORD_LOSS_MAX_Q = 128                         # BMHRL_WORD_LOSS_MAX_Q of include/bmhrl_hip.h
+WORD_LOSS_MAX_L = 64                          # BMHRL_WORD_LOSS_MAX_L
+
+
+def _rows_ld(x, shape, what):
+    """leading dimension of the B * Q fp32 rows of x (B, Q, C): unit column stride and ONE row stride >= C throughout (a
+    view of the first C columns of a wider buffer qualifies)"""
+    if x.dtype != torch.float32 or tuple(x.shape) != tuple(shape):
+        raise ValueError(f"{what}: expected an fp32 tensor of shape {tuple(shape)}")
+    B, Q, Cn = shape
+    ld = x.stride(1) if Q > 1 else (x.stride(0) if B > 1 else Cn)
+    if (Cn > 1 and x.stride(2) != 1) or ld < Cn or (Q > 1 and B > 1 and x.stride(0) != Q * ld):
+        raise ValueError(f"{what}: rows must have unit column stride and one row stride >= {Cn}")
+    return ld
+
+
+def word_cost(logits, captions, pad_idx, cost_scale=1.0):
+    """the cost pass of the DETR word loss (see bmhrl_word_cost in include/bmhrl_hip.h): logits (B, Q, C) fp32 whose rows
+    may sit in a wider buffer (any row stride >= C), captions (B, L) int64.  Returns words (B, L) int32, n_words (B) int32,
+    lse (2, B, Q) -- the log-sum-exp and the rounding residue of its last addition, an fp32 pair the later launches subtract
+    together --, x_none (B, Q), gathered (B, Q, L) and cost (B, Q, L) fp32."""
+    _need_cuda(logits, captions)
+    if logits.dim() != 3 or captions.dim() != 2 or captions.dtype != torch.int64 or captions.shape[0] != logits.shape[0] or \
+            (captions.shape[1] > 1 and captions.stride(1) != 1):
+        raise ValueError("word_cost: logits (B, Q, C) fp32 and captions (B, L) int64 with contiguous rows expected")
+    B, Q, Cn = logits.shape
+    L = captions.shape[1]
+    ld = _rows_ld(logits, (B, Q, Cn), "word_cost")
+    dev = logits.device
+    words = torch.empty(B, L, dtype=torch.int32, device=dev)
+    n_words = torch.empty(B, dtype=torch.int32, device=dev)
+    lse = torch.empty(2, B, Q, device=dev)
+    x_none = torch.empty(B, Q, device=dev)
+    gathered = torch.empty(B, Q, L, device=dev)
+    cost = torch.empty(B, Q, L, device=dev)
+    _lib.check(_lib.load().bmhrl_word_cost(logits.data_ptr(), ld, captions.data_ptr(), captions.stride(0) if B > 1 else max(L, 1),
+                                           int(pad_idx), float(cost_scale), B, Q, L, Cn, words.data_ptr(), n_words.data_ptr(),
+                                           lse[0].data_ptr(), lse[1].data_ptr(), x_none.data_ptr(), gathered.data_ptr(),
+                                           cost.data_ptr(), stream()), "bmhrl_word_cost")
+    return words, n_words, lse, x_none, gathered, cost
+
+
+def lsa_match(cost, n, out=None):
+    """minimum-cost assignment per sample (see bmhrl_lsa_match): cost (B, Q, L) fp32 with any positive strides, n (B) int32
+    targets per sample.  Returns query_of_target (B, L) int32: a distinct query for each target j < n[b], -1 behind them."""
+    _need_cuda(cost, n, out)
+    if cost.dim() != 3 or cost.dtype != torch.float32 or n.dtype != torch.int32 or n.numel() != cost.shape[0] or \
+            not n.is_contiguous():
+        raise ValueError("lsa_match: cost (B, Q, L) fp32 and n (B) int32 expected")
+    B, Q, L = cost.shape
+    if out is None:
+        out = torch.empty(B, L, dtype=torch.int32, device=cost.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (B, L) or not out.is_contiguous():
+        raise ValueError("lsa_match: out must be a contiguous (B, L) int32 tensor")
+    sb, sq, sl = (s if d > 1 else 1 for s, d in zip(cost.stride(), cost.shape))
+    _lib.check(_lib.load().bmhrl_lsa_match(cost.data_ptr(), sb, sq, sl, n.data_ptr(), B, Q, L, out.data_ptr(), stream()),
+               "bmhrl_lsa_match")
+    return out
+
+
+def word_loss(words, n_words, query_of_target, lse, x_none, gathered, eos_coef, C):
+    """class map, row weights and the weighted mean (see bmhrl_word_loss).  Returns tgt_class (B, Q) int32, row_w (B, Q)
+    fp32 and loss_scale (2,) fp32 = [loss, 1 / sum row_w]."""
+    _need_cuda(words, n_words, query_of_target, lse, x_none, gathered)
+    if gathered.dim() != 3:
+        raise ValueError("word_loss: gathered must be (B, Q, L)")
+    B, Q, L = gathered.shape
+    for t, shape, dt in ((words, (B, L), torch.int32), (n_words, (B,), torch.int32), (query_of_target, (B, L), torch.int32),
+                         (lse, (2, B, Q), torch.float32), (x_none, (B, Q), torch.float32), (gathered, (B, Q, L), torch.float32)):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"word_loss: expected a contiguous {dt} tensor of shape {shape}")
+    dev = gathered.device
+    tgt_class = torch.empty(B, Q, dtype=torch.int32, device=dev)
+    row_w = torch.empty(B, Q, device=dev)
+    loss_scale = torch.empty(2, device=dev)
+    _lib.check(_lib.load().bmhrl_word_loss(words.data_ptr(), n_words.data_ptr(), query_of_target.data_ptr(), lse[0].data_ptr(),
+                                           lse[1].data_ptr(), x_none.data_ptr(), gathered.data_ptr(), float(eos_coef), B, Q, L, int(C),
+                                           tgt_class.data_ptr(), row_w.data_ptr(), loss_scale.data_ptr(), stream()),
+               "bmhrl_word_loss")
+    return tgt_class, row_w, loss_scale
+
+
+def word_loss_bwd(logits, lse, tgt_class, row_w, loss_scale, g=None, out=None):
+    """d loss / d logits (see bmhrl_word_loss_bwd): logits (B, Q, C) fp32 and lse (2, B, Q) as word_cost takes and
+    returns them; g: None or a (1,) fp32
+    device scalar, the incoming gradient; out: None or (B, Q, C) fp32 rows in a buffer of any row stride >= C, whose
+    padding columns are left alone."""
+    _need_cuda(logits, lse, tgt_class, row_w, loss_scale, g, out)
+    if logits.dim() != 3:
+        raise ValueError("word_loss_bwd: logits must be (B, Q, C)")
+    B, Q, Cn = logits.shape
+    ld = _rows_ld(logits, (B, Q, Cn), "word_loss_bwd")
+    if out is None:
+        out = torch.empty(B, Q, Cn, device=logits.device)
+    ldd = _rows_ld(out, (B, Q, Cn), "word_loss_bwd (out)")
+    for t, n, dt in ((lse, 2 * B * Q, torch.float32), (tgt_class, B * Q, torch.int32), (row_w, B * Q, torch.float32),
+                     (loss_scale, 2, torch.float32)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"word_loss_bwd: expected a contiguous {dt} tensor of {n} elements")
+    if g is not None and (g.dtype != torch.float32 or g.numel() != 1):
+        raise ValueError("word_loss_bwd: g is a (1,) fp32 device scalar")
+    _lib.check(_lib.load().bmhrl_word_loss_bwd(logits.data_ptr(), ld, lse.data_ptr(), lse.data_ptr() + 4 * B * Q,
+                                               tgt_class.data_ptr(), row_w.data_ptr(), loss_scale.data_ptr(), _p(g), out.data_ptr(), ldd, B, Q, Cn, stream()),
+               "bmhrl_word_loss_bwd")
+    return out

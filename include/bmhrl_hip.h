@@ -702,6 +702,48 @@ int bmhrl_logit_rules(float* logp, int64_t ld, int32_t rows, int32_t V, const in
 int bmhrl_consensus(const int64_t* hist, int64_t ld, int32_t B, int32_t K, int32_t steps, int64_t end_idx, int32_t N,
                     const float* token_weight, int32_t V, double* util, double* pair, bmhrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The DETR word loss (bmhrl_amd/loss/hungarian_matcher.py): the caption's words are matched one to
+ * one to the detector's Q queries by minimum total cost -cost_scale * p(word | query), and the class logits are scored by
+ * the cross entropy with weight eos_coef on the rows of unmatched queries, whose class is "no word" (the last, C - 1).
+ * Four ordinary launches, ordered by the stream alone; none synchronises across blocks or uses atomics, and equal inputs
+ * give equal bits.  B, Q, L >= 1, Q <= BMHRL_WORD_LOSS_MAX_Q, L <= BMHRL_WORD_LOSS_MAX_L, L <= Q, C >= 2, leading
+ * dimensions >= C, B * Q <= INT32_MAX; other shapes and null required pointers are refused with -22 and launch nothing.
+ *
+ * bmhrl_word_cost: logits (B * Q, C) fp32 with leading dimension ld (any ld >= C: rows need only 4-byte alignment; columns
+ *  C .. ld-1 are never read); captions (B, L) int64, row stride ldc.  The words of sample b are its entries != pad_idx, in
+ *  order, wherever the pads sit; an id outside [0, C - 2] is dropped like a pad, so no row is ever indexed outside
+ *  [0, C).  Writes words (B, L) int32 (-1 behind the n_b words), n_words (B) int32, and per row r = b * Q + q:
+ *  lse[r] = log sum exp of the row (maximum subtracted) with lse_lo[r] the rounding residue of its last addition (the
+ *  pair lse + lse_lo is what the other launches subtract: DESIGN.md section 20), x_none[r] = x[C - 1],
+ *  gathered[r][j] = x[words[b][j]] and cost[r][j] = cost_scale * -exp(gathered - lse - lse_lo) for j < n_b, both 0 for
+ *  j >= n_b (gathered, cost: (B, Q, L) fp32).
+ * bmhrl_lsa_match: rectangular minimum-cost assignment, nothing word-specific.  cost (B, Q, L) fp32 with element strides
+ *  sb, sq, sl; n (B) int32, clamped to [0, L].  Writes query_of_target (B, L) int32: targets 0 .. n_b-1 get distinct
+ *  queries of minimum total cost, the rest -1.  One wavefront per sample, shortest augmenting paths with fp64 duals,
+ *  every tie to the lowest query index.  Entries of targets >= n_b are never read.  A non-finite cost cannot hang or
+ *  misindex the kernel; the matching is then unspecified (a target may stay at -1).
+ * bmhrl_word_loss: tgt_class (B, Q) int32 = the word matched to the query or C - 1; row_w (B, Q) fp32 = 1 or eos_coef;
+ *  loss_scale[0] = sum row_w (lse + lse_lo - x_t) / sum row_w, loss_scale[1] = 1 / sum row_w, summed in fp64 in a fixed order; x_t
+ *  comes from gathered / x_none.  query_of_target entries outside [0, Q) match nothing; a query named twice takes the
+ *  later target.
+ * bmhrl_word_loss_bwd: dlogits[r][c] = g * row_w[r] * loss_scale[1] * (exp(x[r][c] - lse[r] - lse_lo[r]) - [c == tgt_class[r]]) for
+ *  c < C, into fp32 rows of leading dimension ldd (columns C .. ldd-1 are not written).  g: device scalar, null = 1.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_WORD_LOSS_MAX_Q 128
+#define BMHRL_WORD_LOSS_MAX_L 64
+int bmhrl_word_cost(const float* logits, int64_t ld, const int64_t* captions, int64_t ldc, int64_t pad_idx, float cost_scale,
+                    int32_t B, int32_t Q, int32_t L, int32_t C, int32_t* words, int32_t* n_words, float* lse, float* lse_lo,
+                    float* x_none, float* gathered, float* cost, bmhrl_stream_t stream);
+int bmhrl_lsa_match(const float* cost, int64_t sb, int64_t sq, int64_t sl, const int32_t* n, int32_t B, int32_t Q, int32_t L,
+                    int32_t* query_of_target, bmhrl_stream_t stream);
+int bmhrl_word_loss(const int32_t* words, const int32_t* n_words, const int32_t* query_of_target, const float* lse,
+                    const float* lse_lo, const float* x_none, const float* gathered, float eos_coef, int32_t B, int32_t Q,
+                    int32_t L, int32_t C, int32_t* tgt_class, float* row_w, float* loss_scale, bmhrl_stream_t stream);
+int bmhrl_word_loss_bwd(const float* logits, int64_t ld, const float* lse, const float* lse_lo, const int32_t* tgt_class,
+                        const float* row_w, const float* loss_scale, const float* g, float* dlogits, int64_t ldd, int32_t B,
+                        int32_t Q, int32_t C, bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
