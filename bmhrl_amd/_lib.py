@@ -119,6 +119,12 @@ PROTOTYPES = {
     "bmhrl_rnn_step": [i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32, i32, i32, ptr],
     "bmhrl_rnn_wavefront": [ptr, i32, i32, i32, i32, i32, ptr],
     "bmhrl_critic_head": [ptr, ptr, ptr, f32, ptr, ptr, i64, i32, ptr],
+    "bmhrl_rnn_step_train": [i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32, i32, i32, ptr],
+    "bmhrl_rnn_bwd_step": [i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i32, i32, i32, i32, ptr],
+    "bmhrl_gemm_f32_nn": [ptr, i64, i32, ptr, i64, ptr, i64, i32, i32, i32, ptr],
+    "bmhrl_rnn_bias_grad": [ptr, ptr, ptr, ptr, i64, i32, ptr],
+    "bmhrl_arelu_grad": [ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, ptr],
+    "bmhrl_critic_head_loss": [ptr, ptr, ptr, ptr, ptr, f32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, i32, ptr],
     "bmhrl_adam_step": [ptr, ptr, ptr, ptr, i64, f32, f32, f32, f32, f32, i32, ptr, f32, ptr],
     "bmhrl_make_masks": [ptr, i64, ptr, i64, ptr, i32, i32, i32, i32, i64, i32, ptr, ptr, ptr, ptr],
     "bmhrl_batch_head": [ptr, i64, ptr, i64, ptr, i64, i32, i32, i32, i32, i64, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr],

@@ -2193,3 +2193,123 @@ class DetrWordLossFn(torch.autograd.Function):
         x, lse, tgt_class, row_w, loss_scale = ctx.saved_tensors
         g = ops.word_loss_bwd(x, lse, tgt_class, row_w, loss_scale, dloss.reshape(1).float().contiguous())
         return (g if ctx.in_dtype == torch.float32 else g.to(ctx.in_dtype)), None, None, None, None, None
+
+
+_CRITIC_LAYERS = ((4, False), (4, False), (4, False), (4, True), (3, False), (3, True))   # (gates, ends a stack: AReLU)
+
+
+class SegmentCriticFn(torch.autograd.Function):
+    """The segment critic LSTM(4) -> AReLU -> GRU(2) -> AReLU -> Linear, differentiable (csrc/critic_train.hip), fp32.
+    apply(emb (B, L, d), the 24 RNN parameters (lstm l0..l3, gru l0..l1; weight_ih, weight_hh, bias_ih, bias_hh each),
+    relu.alpha, relu.beta, relu2.alpha, relu2.beta, lin.weight, lin.bias) -> score (B, L, 1).
+    With three more arguments (labels (B, L) fp32, mask (B, L) bool, pos_weight float) the head and the masked
+    BCE-with-logits run as one launch and the call returns (score, loss): loss is the differentiable output, the score
+    of that call is not.  Forward: gemm_f32 input projection + one rnn_step_train per (layer, t); backward, top layer
+    down: one rnn_bwd_step per (layer, t), then dX / dW_ih / dW_hh (gemm_f32_nn), the bias sums and the AReLU sums.
+    Every sum is ordered: two runs give the same bits."""
+
+    @staticmethod
+    def forward(ctx, emb, *args):
+        if len(args) not in (30, 33):
+            raise TypeError("SegmentCriticFn takes emb, 30 parameters and optionally labels, mask, pos_weight")
+        params, extra = args[:30], args[30:]
+        ops._need_cuda(emb, *params)
+        B, L, d = emb.shape
+        rows, H, dev = B * L, params[1].shape[1], emb.device
+        x = emb.detach().float().contiguous().view(rows, d)
+        params = [p.detach() for p in params]
+        acts = {3: (params[24], params[25]), 5: (params[26], params[27])}
+        lin_w, lin_b = params[28], params[29]
+        saved = []
+        for li, (G, last) in enumerate(_CRITIC_LAYERS):
+            w_ih, w_hh, b_ih, b_hh = params[4 * li:4 * li + 4]
+            alpha, beta = acts.get(li, (None, None))
+            xproj = torch.empty(rows, G * H, device=dev)
+            ops.gemm_f32(x, w_ih, b_ih, b_hh if G == 4 else None, xproj, rows, G * H, x.shape[1])
+            h_seq, hprev = torch.empty(rows, H, device=dev), torch.empty(rows, H, device=dev)
+            c_seq = torch.empty(rows, H, device=dev) if G == 4 else None
+            hn_seq = torch.empty(rows, H, device=dev) if G == 3 else None
+            gate_seq = torch.empty(rows, G * H, device=dev)
+            y_seq = torch.empty(rows, H, device=dev) if last else None
+            for t in range(L):
+                ops.rnn_step_train(G, xproj, w_hh, b_hh if G == 3 else None, h_seq, hprev, c_seq, gate_seq, hn_seq, y_seq, alpha, beta,
+                                   B, L, H, t)
+            saved += [x, h_seq, hprev, c_seq, gate_seq, hn_seq]
+            x = y_seq if last else h_seq
+        score = torch.empty(B, L, 1, device=dev)
+        ctx.dims = (B, L, d, H)
+        ctx.with_loss = bool(extra)
+        if extra:
+            labels, mask, pw = extra
+            ops._need_cuda(labels, mask)
+            labels = labels.detach().float().contiguous()
+            mask = mask.detach().to(torch.bool).contiguous()
+            loss = torch.empty((), device=dev)
+            ds = torch.empty(rows, device=dev)
+            dy2 = torch.empty(rows, H, device=dev)
+            dlw, dlb = torch.empty(1, H, device=dev), torch.empty(1, device=dev)
+            ops.critic_head_loss(x, lin_w, lin_b, labels, mask, float(pw), None, score, loss, ds, dy2, dlw, dlb, rows, H)
+            ctx.save_for_backward(*params, *saved, dy2, dlw, dlb)
+            ctx.mark_non_differentiable(score)
+            return score, loss
+        ops.critic_head(x, lin_w, lin_b, 0.0, score, None, rows, H)
+        ctx.save_for_backward(*params, *saved, x)
+        return score
+
+    @staticmethod
+    def backward(ctx, dscore, dloss=None):
+        B, L, d, H = ctx.dims
+        rows = B * L
+        t_ = ctx.saved_tensors
+        params, saved, tail = t_[:30], t_[30:66], t_[66:]
+        dev = params[0].device
+        need = ctx.needs_input_grad
+        grads = [None] * 30
+        if ctx.with_loss:
+            g = dloss.float()
+            dy, dlw, dlb = tail[0] * g, tail[1] * g, tail[2] * g
+        else:
+            y2 = tail[0]
+            ds_in = dscore.float().contiguous().view(rows)
+            ds = torch.empty(rows, device=dev)
+            dy = torch.empty(rows, H, device=dev)
+            dlw, dlb = torch.empty(1, H, device=dev), torch.empty(1, device=dev)
+            ops.critic_head_loss(y2, params[28], params[29], None, None, 1.0, ds_in, None, None, ds, dy, dlw, dlb, rows, H)
+        grads[28], grads[29] = (dlw if need[29] else None), (dlb if need[30] else None)
+        acts = {3: 24, 5: 26}
+        demb = None
+        for li in range(5, -1, -1):
+            G, last = _CRITIC_LAYERS[li]
+            w_ih, w_hh = params[4 * li], params[4 * li + 1]
+            x_in, h_seq, hprev, c_seq, gate_seq, hn_seq = saved[6 * li:6 * li + 6]
+            K = x_in.shape[1]
+            alpha, beta = (params[acts[li]], params[acts[li] + 1]) if last else (None, None)
+            dax = torch.empty(rows, G * H, device=dev)
+            dah = torch.empty(rows, G * H, device=dev) if G == 3 else None
+            carry = torch.empty(B, H, device=dev)
+            for t in range(L - 1, -1, -1):
+                ops.rnn_bwd_step(G, w_hh, dy, h_seq, c_seq, gate_seq, hn_seq, carry, dax, dah, alpha, beta, B, L, H, t)
+            if last and (need[1 + acts[li]] or need[2 + acts[li]]):
+                da, db = torch.empty(1, device=dev), torch.empty(1, device=dev)
+                ops.arelu_grad(dy, h_seq, alpha, beta, da, db, rows * H)
+                grads[acts[li]], grads[acts[li] + 1] = (da if need[1 + acts[li]] else None), (db if need[2 + acts[li]] else None)
+            n_ih, n_hh, n_bi, n_bh = need[1 + 4 * li:5 + 4 * li]
+            if n_ih:
+                grads[4 * li] = torch.empty(G * H, K, device=dev)
+                ops.gemm_f32_nn(dax, x_in, grads[4 * li], G * H, K, rows, a_kmajor=True)
+            if n_hh:
+                grads[4 * li + 1] = torch.empty(G * H, H, device=dev)
+                ops.gemm_f32_nn(dah if G == 3 else dax, hprev, grads[4 * li + 1], G * H, H, rows, a_kmajor=True)
+            if n_bi or n_bh:
+                dbx = torch.empty(G * H, device=dev)
+                dbh = torch.empty(G * H, device=dev) if G == 3 else None
+                ops.rnn_bias_grad(dax, dah, dbx, dbh, rows, G * H)
+                grads[4 * li + 2] = dbx if n_bi else None
+                grads[4 * li + 3] = (dbh if G == 3 else dbx.clone()) if n_bh else None
+            if li > 0 or need[0]:
+                dx = torch.empty(rows, K, device=dev)
+                ops.gemm_f32_nn(dax, w_ih, dx, rows, K, G * H)
+                dy = dx
+                if li == 0:
+                    demb = dx.view(B, L, d)
+        return (demb, *grads) + ((None, None, None) if ctx.with_loss else ())

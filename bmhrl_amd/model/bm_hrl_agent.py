@@ -292,6 +292,37 @@ class SegmentCritic(nn.Module):
             h, _ = self.gru(self.relu(h))
             return self.lin(self.relu2(h))
 
+    def train_parameters(self):
+        """the 30 parameters in SegmentCriticFn's order: the 24 of lstm l0..l3 and gru l0..l1, the two AReLUs, the head"""
+        ps = [getattr(rnn, f"{k}_l{l}") for rnn, n in ((self.lstm, 4), (self.gru, 2)) for l in range(n)
+              for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        return ps + [self.relu.alpha, self.relu.beta, self.relu2.alpha, self.relu2.beta, self.lin.weight, self.lin.bias]
+
+    def score(self, emb):
+        """Differentiable score (B, L, 1) on the HIP training kernels (functional.SegmentCriticFn: layer by layer, every
+        sum ordered).  forward() / score_and_labels() stay the no-grad inference path."""
+        from ..functional import SegmentCriticFn
+        return SegmentCriticFn.apply(emb, *self.train_parameters())
+
+    def masked_bce(self, emb, labels, mask, pos_weight=1.0):
+        """(loss, score): the masked BCE-with-logits of score(emb) against labels (B, L), sum(mask * l) / sum(mask), head and
+        loss in one launch.  The loss is differentiable; the score returned beside it is not."""
+        from ..functional import SegmentCriticFn
+        score, loss = SegmentCriticFn.apply(emb, *self.train_parameters(), labels, mask, float(pos_weight))
+        return loss, score
+
+    def unfreeze(self):
+        """Make the parameters trainable (critic_train.CriticTrainer).  Only for a standalone critic: a CaptionTrainer builds
+        its flat bucket from requires_grad, so an agent's own critic must stay frozen while a trainer holds the agent."""
+        for p in self.parameters():
+            p.requires_grad = True
+        return self
+
+    def freeze(self):
+        for p in self.parameters():
+            p.requires_grad = False
+        return self
+
     wavefront = True       # False: one GEMM + L step launches per layer (the first native form; kept for A/B and tests)
     # time steps a layer trails the one below: W_ih is read once per chunk (ops.rnn_wavefront).  r03 re-measured the step at
     # chunk 1 / 2 / 3 / 5 on one box: 5.634 / 5.637 / 5.65 / 5.651 ms -- the chunk machinery no longer pays; default 1 (the

@@ -636,6 +636,50 @@ def critic_head(x, w, b, threshold, score, labels, rows, H):
                                              stream()), "bmhrl_critic_head")
 
 
+def rnn_step_train(gates, xproj, whh, bhh, h_seq, hprev_seq, c_seq, gate_seq, hn_seq, y_seq, ar_alpha, ar_beta, B, L, H, t):
+    """one training-forward time step of one layer (bmhrl_rnn_step_train): rnn_step that keeps what the backward needs"""
+    _need_cuda(xproj, whh, bhh, h_seq, hprev_seq, c_seq, gate_seq, hn_seq, y_seq, ar_alpha, ar_beta)
+    _lib.check(_lib.load().bmhrl_rnn_step_train(gates, _p(xproj), _p(whh), _p(bhh), _p(h_seq), _p(hprev_seq), _p(c_seq), _p(gate_seq), _p(hn_seq),
+                                                _p(y_seq), _p(ar_alpha), _p(ar_beta), B, L, H, t, stream()), "bmhrl_rnn_step_train")
+
+
+def rnn_bwd_step(gates, whh, dy, h_seq, c_seq, gate_seq, hn_seq, carry, dax, dah, ar_alpha, ar_beta, B, L, H, t):
+    """backward of one cell, t descending (bmhrl_rnn_bwd_step); the LSTM passes dah=None"""
+    _need_cuda(whh, dy, h_seq, c_seq, gate_seq, hn_seq, carry, dax, dah, ar_alpha, ar_beta)
+    _lib.check(_lib.load().bmhrl_rnn_bwd_step(gates, _p(whh), _p(dy), _p(h_seq), _p(c_seq), _p(gate_seq), _p(hn_seq), _p(carry),
+                                              _p(dax), _p(dah), _p(ar_alpha), _p(ar_beta), B, L, H, t, stream()), "bmhrl_rnn_bwd_step")
+
+
+def gemm_f32_nn(A, Bm, C, M, N, K, a_kmajor=False):
+    """C[M,N] = op(A) . B, B (K, N) row-major; A (M, K) row-major or, a_kmajor, (K, M) row-major (bmhrl_gemm_f32_nn)"""
+    _need_cuda(A, Bm, C)
+    _lib.check(_lib.load().bmhrl_gemm_f32_nn(_p(A), 0 if A is None else A.stride(0), int(a_kmajor), _p(Bm),
+                                             0 if Bm is None else Bm.stride(0), _p(C), 0 if C is None else C.stride(0), M, N, K,
+                                             stream()), "bmhrl_gemm_f32_nn")
+
+
+def rnn_bias_grad(dax, dah, db_x, db_h, rows, N):
+    _need_cuda(dax, dah, db_x, db_h)
+    _lib.check(_lib.load().bmhrl_rnn_bias_grad(_p(dax), _p(dah), _p(db_x), _p(db_h), rows, N, stream()), "bmhrl_rnn_bias_grad")
+
+
+def arelu_grad(dy, h, alpha, beta, dalpha, dbeta, n):
+    """ordered AReLU parameter gradients over n elements (bmhrl_arelu_grad)"""
+    _need_cuda(dy, h, alpha, beta, dalpha, dbeta)
+    partial = None if dy is None else torch.empty(128, device=dy.device)
+    _lib.check(_lib.load().bmhrl_arelu_grad(_p(dy), _p(h), _p(alpha), _p(beta), _p(partial), _p(dalpha), _p(dbeta), n, stream()),
+               "bmhrl_arelu_grad")
+
+
+def critic_head_loss(y2, lin_w, lin_b, labels, mask, pos_weight, ds_in, score, loss, ds, dy2, dlin_w, dlin_b, rows, H):
+    """head (+ masked BCE-with-logits when labels is given) and its backward in one launch (bmhrl_critic_head_loss);
+    mask: bool / uint8, one byte per row"""
+    _need_cuda(y2, lin_w, lin_b, labels, mask, ds_in, score, loss, ds, dy2, dlin_w, dlin_b)
+    _lib.check(_lib.load().bmhrl_critic_head_loss(_p(y2), _p(lin_w), _p(lin_b), _p(labels), _p(mask), float(pos_weight), _p(ds_in),
+                                                  _p(score), _p(loss), _p(ds), _p(dy2), _p(dlin_w), _p(dlin_b), rows, H, stream()),
+               "bmhrl_critic_head_loss")
+
+
 def adam_segments(table, n_segments, n_blocks, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step,
                   grad_scale=1.0, step_dev=None, hyper=None):
     """Adam over the flat bucket through a per-parameter table that also names each weight's bf16 shadow (see

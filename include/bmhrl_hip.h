@@ -481,6 +481,45 @@ int bmhrl_critic_head(const float* x, const float* w, const float* b, float thre
                       int64_t rows, int32_t H, bmhrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training the segment critic (csrc/critic_train.hip), fp32, zero initial state, every sum in a fixed order (no float
+ * atomics: two runs agree bit for bit).  Sequence buffers have row b*L + t.
+ *  bmhrl_rnn_step_train  : bmhrl_rnn_step's cell with the recurrent product on the f32 matrix pipe (k split over the waves);
+ *                          keeps the raw h_t in h_seq (B*L, H), h_{t-1} in hprev_seq (B*L, H) (zero at t = 0; step t reads its
+ *                          row t and writes row t + 1), c_t in c_seq (LSTM), the gate activations i,f,g,o / r,z,n in gate_seq
+ *                          (B*L, gates*H), W_hn h_{t-1} + b_hn in hn_seq (GRU) and AReLU(h_t) in y_seq when arelu_alpha /
+ *                          arelu_beta are given
+ *  bmhrl_rnn_bwd_step    : backward of one cell, called with t descending from L - 1.  dy (B*L, H) is the gradient of the
+ *                          layer's output sequence (of y_seq when the AReLU parameters are given).  The launch of step t forms
+ *                          the carried dh = dA_h[t + 1] . W_hh (f32 matrix pipe, k split over the waves), runs the cell
+ *                          equations and writes row t of dax / dah (B*L, gates*H; the LSTM has one buffer: dah is ignored) and
+ *                          the element-wise carry (B, H) (LSTM dc . f, GRU dh . z; not read at t = L - 1)
+ *  bmhrl_gemm_f32_nn     : C[M,N] = op(A) . B, B (K, N) row-major, A (M, K) row-major (K % 4 == 0) or, a_kmajor, (K, M)
+ *                          row-major (any K): dX = dA_x . W_ih, dW_ih = dA_x^T . X, dW_hh = dA_h^T . H_prev (hprev_seq)
+ *  bmhrl_rnn_bias_grad   : db_x = column sums of dax (rows, N); db_h of dah when given
+ *  bmhrl_arelu_grad      : dbeta = sum dy relu(h) s(beta)(1 - s(beta)); dalpha = -sum dy relu(-h) for 0.01 <= alpha <= 0.99, else
+ *                          0; partial: 128 floats of scratch
+ *  bmhrl_critic_head_loss: one launch.  labels given: score = lin_w . y2 + lin_b, loss = sum mask l / sum mask with the
+ *                          BCE-with-logits l of positive weight pos_weight, ds = d loss / d score; labels null: ds = ds_in.
+ *                          Then dy2 = ds lin_w, dlin_w = sum ds y2, dlin_b = sum ds.  mask: one byte per row.
+ * ------------------------------------------------------------------------------------------- */
+int bmhrl_rnn_step_train(int32_t gates, const float* xproj, const float* whh, const float* bhh, float* h_seq, float* hprev_seq,
+                         float* c_seq, float* gate_seq, float* hn_seq, float* y_seq, const float* arelu_alpha,
+                         const float* arelu_beta, int32_t B, int32_t L, int32_t H, int32_t t, bmhrl_stream_t stream);
+int bmhrl_rnn_bwd_step(int32_t gates, const float* whh, const float* dy, const float* h_seq, const float* c_seq,
+                       const float* gate_seq, const float* hn_seq, float* carry, float* dax, float* dah,
+                       const float* arelu_alpha, const float* arelu_beta, int32_t B, int32_t L, int32_t H, int32_t t,
+                       bmhrl_stream_t stream);
+int bmhrl_gemm_f32_nn(const float* A, int64_t lda, int32_t a_kmajor, const float* Bm, int64_t ldb, float* C, int64_t ldc,
+                      int32_t M, int32_t N, int32_t K, bmhrl_stream_t stream);
+int bmhrl_rnn_bias_grad(const float* dax, const float* dah, float* db_x, float* db_h, int64_t rows, int32_t N,
+                        bmhrl_stream_t stream);
+int bmhrl_arelu_grad(const float* dy, const float* h, const float* alpha, const float* beta, float* partial, float* dalpha,
+                     float* dbeta, int64_t n, bmhrl_stream_t stream);
+int bmhrl_critic_head_loss(const float* y2, const float* lin_w, const float* lin_b, const float* labels, const uint8_t* mask,
+                           float pos_weight, const float* ds_in, float* score, float* loss, float* ds, float* dy2,
+                           float* dlin_w, float* dlin_b, int64_t rows, int32_t H, bmhrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Optimiser (K14): torch.optim.Adam semantics (scripts/train_rl_captioning_module.py:81-83, default
  * betas/eps, L2 weight decay added to the gradient) over one flat fp32 bucket; grad_scale multiplies
  * the gradient first (1/world for data parallel averaging).
