@@ -375,7 +375,13 @@ int bmhrl_gather_rows(const float* x, const int32_t* src, float* out, void* out_
                       int32_t D, bmhrl_stream_t stream);
 /* backward of the gather along a row map of bmhrl_expand_goals[_index]: dx[s] = sum of dout[r] over src[r] == s, every row of dx
  * written.  The map's structure is used (a run of consecutive rows points at its LAST row, other rows at themselves or at -1):
- * the sum runs in row order, no atomics -- the manager's goal gradient is the same from run to run. */
+ * the sum runs in row order, no atomics -- the manager's goal gradient is the same from run to run.
+ * dx, the contract: callers pass a ZEROED (rows, D) buffer and a map whose entries are -1 or in [0, rows).  The two modes differ
+ * in what they do with dx, and a zeroed buffer is the one input on which they agree:
+ *   default:               every element of dx is OVERWRITTEN (rows that nothing points at get 0); only the row maps of
+ *                          bmhrl_expand_goals[_index] are summed correctly -- a general map is not supported;
+ *   BMHRL_DETERMINISTIC=1: one thread per column walks the rows in order and ACCUMULATES into dx (dx[src[r]] += dout[r]); any
+ *                          map is handled, and whatever dx held before stays in the sum. */
 int bmhrl_scatter_add_rows(const float* dout, const int32_t* src, float* dx, int64_t rows, int32_t D,
                            bmhrl_stream_t stream);
 
