@@ -135,6 +135,8 @@ PROTOTYPES = {
     "bmhrl_accum_segments": [ptr, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr],
     "bmhrl_beam_select": [ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, i32, ptr, ptr, i32, i32, i32, i32, i32, ptr],
     "bmhrl_beam_reorder": [ptr, i32, i64, ptr, i32, i32, ptr, i32, ptr],
+    "bmhrl_group_beam_select": [ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, i32, ptr, ptr, i32, i32, i32, i32, i32, i32,
+                                f32, ptr],
     "bmhrl_rewards": [ptr, i64, ptr, i32, i64, ptr, i64, ptr, ptr, ptr, i32, i32, i32, f64, i32, i32, i32, ptr, i64, ptr, i64,
                       ptr],
     "bmhrl_meteor": [ptr, i64, ptr, ptr, i32, ptr, ptr, i32, ptr, ptr, i64, ptr, f64, f64, f64, i32, i32, i32, ptr, i64, ptr,

@@ -18,6 +18,8 @@ Every decoder takes no_repeat_ngram / min_len / repetition_penalty (the constrai
 log-probs before the choice, in the captured step through one HIP launch.
 beam_decode / sample_decode take select="consensus" (the consensus section): the returned caption is the hypothesis that
 agrees most with the clip's other hypotheses, one HIP launch after the token loop.
+beam_decode takes beam_groups / diversity_penalty (the group beam search section): diverse beam search, the beams in groups
+that choose one after another (GroupBeamDecoder: one grouped selection launch in place of the plain one, or re-runs).
 """
 import math
 import random
@@ -555,7 +557,8 @@ def _apply_rules(lp, hist, t, ngram, min_len, penalty, end_idx, pad_idx):
 
 def beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, beam_size=4, length_penalty=0.0,
                 return_scores=False, return_beams=False, incremental=None, no_repeat_ngram=0, min_len=0,
-                repetition_penalty=1.0, select="logp", consensus_n=4, consensus_weight=None):
+                repetition_penalty=1.0, select="logp", consensus_n=4, consensus_weight=None, beam_groups=1,
+                diversity_penalty=0.0, return_groups=False):
     """Beam search with the reference decoder's arguments.  Returns tokens (B, n + 1) int64, then -- when asked -- the
     chosen hypotheses' raw scores (B,) fp32, then all K hypotheses sorted best first as tokens (B, K, m + 1) (m: the
     longest n_k of all of them, so that no hypothesis is cut) and raw scores (B, K).
@@ -567,38 +570,51 @@ def beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, mod
     select="consensus" (with consensus_n = N in [1, 4] and consensus_weight = None or a (V,) tensor of token weights)
     replaces rule 5's choice by the consensus section's: the returned tokens and score are those of the hypothesis with the
     largest utility, and return_beams appends the utilities (B, K) fp64 of the returned hypotheses, in their order, as the
-    LAST element of the tuple.  With select="logp" (the default) the tuple is as described above."""
+    LAST element of the tuple.  With select="logp" (the default) the tuple is as described above.
+    beam_groups = G > 1 with diversity_penalty (the group beam search section): diverse beam search, the K beams in G groups
+    of K / G that choose one after another, through GroupBeamDecoder under the conditions BeamDecoder is taken, else over
+    re-runs.  With G = 1 (the default) the search is the plain one above whatever diversity_penalty is.  return_groups (only
+    with return_beams) appends the group index (B, K) int64 of the returned hypotheses, in their order, after the beams'
+    scores and before the consensus utilities."""
     K = int(beam_size)
     if K < 1:
         raise ValueError(f"beam_size must be >= 1, got {beam_size}")
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty, max_len)
     consensus = _consensus_args(select, consensus_n, consensus_weight)
+    G, lam = _group_args(K, beam_groups, diversity_penalty, return_groups, return_beams)
     with torch.no_grad():
-        dec = _incremental(BeamDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, K, incremental,
-                           rules=rules)
-        found = dec.run() if dec is not None else _beam_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
-                                                              modality, K, rules)
-        if consensus is None:
-            return _beam_result(*found, end_idx, length_penalty, return_scores, return_beams)
-        util = _consensus_utilities(dec, found[0], found[2], end_idx, *consensus)
-        return _beam_result(*found, end_idx, length_penalty, return_scores, return_beams, util)
+        if G == 1:
+            dec = _incremental(BeamDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, K,
+                               incremental, rules=rules)
+            found = dec.run() if dec is not None else _beam_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
+                                                                  modality, K, rules)
+        else:
+            dec = _incremental(GroupBeamDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, K,
+                               incremental, params=(G, lam), rules=rules)
+            found = dec.run() if dec is not None else _group_beam_rerun(model, feature_stacks, max_len, start_idx, end_idx,
+                                                                        pad_idx, modality, K, G, lam, rules)
+        util = None if consensus is None else _consensus_utilities(dec, found[0], found[2], end_idx, *consensus)
+        return _beam_result(*found, end_idx, length_penalty, return_scores, return_beams, util,
+                            K // G if return_groups else None)
 
 
 def beam_decoder(beam_size=4, length_penalty=0.0, no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, select="logp",
-                 consensus_n=4, consensus_weight=None):
+                 consensus_n=4, consensus_weight=None, beam_groups=1, diversity_penalty=0.0):
     """a decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality), e.g.
     validation_1by1_loop(cfg, model, loader, beam_decoder(4), epoch, TBoard); select / consensus_n / consensus_weight: the
-    consensus section's choice among the K beams"""
+    consensus section's choice among the K beams; beam_groups / diversity_penalty: the group beam search section's diverse
+    beams, e.g. beam_decoder(8, beam_groups=4, diversity_penalty=0.5, select="consensus")"""
     if int(beam_size) < 1:
         raise ValueError(f"beam_size must be >= 1, got {beam_size}")
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty) or _NO_RULES
     _consensus_args(select, consensus_n, consensus_weight)
+    _group_args(int(beam_size), beam_groups, diversity_penalty)
 
     def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
         return beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, beam_size=beam_size,
                            length_penalty=length_penalty, no_repeat_ngram=rules[0], min_len=rules[1],
                            repetition_penalty=rules[2], select=select, consensus_n=consensus_n,
-                           consensus_weight=consensus_weight)
+                           consensus_weight=consensus_weight, beam_groups=beam_groups, diversity_penalty=diversity_penalty)
     return decoder
 
 
@@ -661,9 +677,10 @@ def _best_hypothesis(toks, scores, steps, end_idx, length_penalty):
     return n_k, order, toks[rows, order[:, 0], :n + 1].clone()
 
 
-def _beam_result(toks, scores, steps, end_idx, length_penalty, return_scores, return_beams, util=None):
+def _beam_result(toks, scores, steps, end_idx, length_penalty, return_scores, return_beams, util=None, group_size=None):
     """rules 5-6 over (B, K, >= steps + 1) hypotheses and their raw scores; util: the hypotheses' consensus utilities (B, K),
-    in the rows' order -- the choice is then consensus rule R7 over rule 5's order"""
+    in the rows' order -- the choice is then consensus rule R7 over rule 5's order; group_size: K' of rule G1 when the
+    returned hypotheses' group indices are asked for (return_groups)"""
     toks = toks[..., :steps + 1]
     n_k, order, best = _best_hypothesis(toks, scores, steps, end_idx, length_penalty)
     chosen = order[:, :1]
@@ -676,6 +693,8 @@ def _beam_result(toks, scores, steps, end_idx, length_penalty, return_scores, re
     if return_beams:
         m = int(n_k.max()) if scores.shape[0] else 0
         out += [toks.gather(1, order.unsqueeze(-1).expand(-1, -1, toks.shape[-1]))[..., :m + 1].clone(), scores.gather(1, order)]
+        if group_size is not None:
+            out.append(torch.div(order, group_size, rounding_mode="floor"))
         if util is not None:
             out.append(util.gather(1, order))
     return out[0] if len(out) == 1 else tuple(out)
@@ -745,6 +764,148 @@ class BeamDecoder(IncrementalDecoder):
         if last < n:
             n = last + 1
         return self.out[:, :n + 1].view(self.B, self.K, n + 1).clone(), self.scores.view(self.B, self.K).clone(), n
+
+
+# ---------------------------------------------------------------------------------------------------- group beam search
+# Diverse beam search (Vijayakumar et al. 2018; elsewhere `num_beam_groups` with a diversity penalty).  Rules (both paths --
+# bmhrl_group_beam_select in the captured token step, _group_beam_rerun over re-runs -- implement exactly these).  Inputs:
+# K beams per sample, G groups (beam_groups; G divides K, K' = K / G), lambda = diversity_penalty (finite, >= 0; the fp32
+# value of the host float).
+#  G1. group g owns beams g*K' .. g*K' + K' - 1 of its sample.  The first beam of every group starts live with score 0 and
+#      input start_idx, the group's other beams start finished with score -inf;
+#  G2. at a step the groups choose in the order g = 0 .. G-1.  c_g(v) = the number of beams of groups 0 .. g-1 of the same
+#      sample whose choice at this step was a candidate (k, v) of a live beam -- for any v, end_idx and pad_idx included; a
+#      finished beam's pad candidate counts for nothing.  c_0 = 0;
+#  G3. a live beam k of group g offers V candidates (k, v) with the score s = score_k + lp(k, v) (one fp32 add, as beam rule
+#      2) and the selection value a = s - lambda * c_g(v): c converted to fp32, one fp32 multiply, then one fp32 subtract, no
+#      FMA contraction.  Where c = 0, a is s bit for bit (-inf included); where the product overflows, IEEE decides.  A
+#      finished beam offers the single candidate (k, pad_idx) with a = s = score_k, never penalised;
+#  G4. the K' best candidates of group g by a become the group's beams, best first, ties to the smaller k*V + v (a stable
+#      sort of -a over the group's candidates): a beam's parent is always in its own group.  The new beam's score is s, not
+#      a -- the penalty steers the choice and is never added to a score, so scores stay sums of (rule-adjusted) log-probs and
+#      beam rule 5, return_scores and the teacher-forced check keep their meaning.  Choosing end_idx finishes a beam;
+#  G5. beam rules 4-6 then apply over all K beams of the sample (the stop, n_k, the choice by length-normalised score with
+#      ties to the lower beam index, the result layout), and consensus R1-R7 with select="consensus".
+# G = 1 is beam search for every lambda (and takes the beam search section's own code).  lambda = 0 makes every group the
+# same K'-beam search: beam g*K' + j equals beam j of beam_size = K', tokens and scores bit for bit.
+# Refused with ValueError: G < 1 or no integer, K % G != 0, lambda negative or non-finite (as fp32 too), return_groups
+# without return_beams.
+
+
+def _group_args(K, beam_groups=1, diversity_penalty=0.0, return_groups=False, return_beams=True):
+    """(G, lambda as the fp32 value the kernel sees) of valid arguments"""
+    try:
+        whole = not isinstance(beam_groups, bool) and int(beam_groups) == beam_groups
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or int(beam_groups) < 1:
+        raise ValueError(f"beam_groups must be an integer >= 1, got {beam_groups!r}")
+    G = int(beam_groups)
+    if K % G:
+        raise ValueError(f"beam_groups must divide beam_size: {K} beams in {G} groups")
+    try:
+        lam = float(diversity_penalty)
+    except (TypeError, ValueError):
+        raise ValueError(f"diversity_penalty must be finite and >= 0, got {diversity_penalty!r}") from None
+    if not (math.isfinite(lam) and lam >= 0 and math.isfinite(_f32(lam))):
+        raise ValueError(f"diversity_penalty must be finite and >= 0, got {diversity_penalty}")
+    if return_groups and not return_beams:
+        raise ValueError("return_groups needs return_beams")
+    return G, _f32(lam)
+
+
+def _group_beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K, G, penalty, rules=None, trace=None):
+    """rules G1-G4 and beam rule 4 over full re-runs of model.inference on the prefix batch -> (tokens (B, K, n + 1),
+    scores (B, K), n); rules: what _rule_args returned.  trace: a list that receives one dict per step -- the step's log-probs
+    `logp` (B, K, V), the `scores` / `finished` it started from and, after it, `parent`, `tok`, `new_scores`, `new_finished`
+    (B, K) and the beams `hist` (B, K, step + 2)."""
+    B = fs['audio'].shape[0]
+    dev = fs['audio'].device
+    Kp = K // G
+    rep, x = _rerun_setup(fs, K)
+    scores = torch.full((B, K), float("-inf"), device=dev)
+    scores[:, ::Kp] = 0.0
+    finished = torch.ones(B, K, dtype=torch.bool, device=dev)
+    finished[:, ::Kp] = False
+    hist = torch.full((B * K, 1), start_idx, dtype=torch.long, device=dev)
+    lam = torch.tensor(penalty, dtype=torch.float32, device=dev)
+    steps = 0
+    while steps < max_len:
+        lp = _rerun_logp(model, x, rep, hist, modality, pad_idx)
+        if rules is not None:
+            lp = _apply_rules(lp, hist, steps, *rules, end_idx, pad_idx)
+        V = lp.shape[-1]
+        cand = scores.unsqueeze(-1) + lp.view(B, K, V)
+        only = torch.zeros_like(cand)
+        only[..., pad_idx] = scores
+        cand = torch.where(finished.unsqueeze(-1), only, cand)                 # s of every candidate (B, K, V)
+        count = torch.zeros(B, V, device=dev)                                  # c_g(v), exact in fp32
+        parent, tok, new_scores = [], [], []
+        for g in range(G):
+            s_g, fin_g = cand[:, g * Kp:(g + 1) * Kp], finished[:, g * Kp:(g + 1) * Kp]
+            pen = count * lam                                                  # one multiply, then one subtract
+            a = torch.where(fin_g.unsqueeze(-1) | (count == 0).unsqueeze(1), s_g, s_g - pen.unsqueeze(1))
+            pick = _stable_top(a.reshape(B, Kp * V), fin_g, pad_idx)
+            p_g, t_g = pick // V, pick % V
+            count.scatter_add_(1, t_g, (~fin_g.gather(1, p_g)).to(count.dtype))
+            parent.append(p_g + g * Kp)
+            tok.append(t_g)
+            new_scores.append(s_g.reshape(B, Kp * V).gather(1, pick))
+        parent, tok, new_scores = torch.cat(parent, 1), torch.cat(tok, 1), torch.cat(new_scores, 1)
+        step = dict(logp=lp.view(B, K, V), scores=scores, finished=finished) if trace is not None else None
+        scores = new_scores
+        finished = finished.gather(1, parent) | (tok == end_idx)
+        hist = hist.view(B, K, -1).gather(1, parent.unsqueeze(-1).expand(-1, -1, hist.shape[-1])).view(B * K, -1)
+        hist = torch.cat([hist, tok.view(B * K, 1)], 1)
+        steps += 1
+        if trace is not None:
+            step.update(parent=parent, tok=tok, new_scores=scores, new_finished=finished, hist=hist.view(B, K, -1))
+            trace.append(step)
+        if bool(finished.all()):
+            break
+    return hist.view(B, K, -1), scores, steps
+
+
+class GroupBeamDecoder(BeamDecoder):
+    """BeamDecoder with bmhrl_group_beam_select (csrc/group_beam.hip: rules G2-G4 for all groups, one launch) in place of
+    bmhrl_beam_select; the two reorder launches, the per-beam buffers, the constraints launch and the result are
+    BeamDecoder's, so the token step has no launch more than plain beam search.  beam_groups / diversity_penalty are launch
+    arguments: set_params() captures the step again when they change, as SampleDecoder's.  A decoder from for_batch starts
+    with G = 1, lambda = 0; _incremental sets both before every clip batch."""
+
+    _cache_attr = "_group_beam_decoders"
+
+    def __init__(self, agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device, beams=4, beam_groups=1,
+                 diversity_penalty=0.0):
+        self.params = _group_args(int(beams), beam_groups, diversity_penalty)
+        super().__init__(agent, B, tv_cap, ta_cap, max_len, start_idx, end_idx, pad_idx, device, beams=beams)
+
+    def set_params(self, beam_groups, diversity_penalty):
+        """not while a clip batch is being decoded: the beams of rule G1 are laid out by the begin() that follows"""
+        params = _group_args(self.K, beam_groups, diversity_penalty)
+        if params != self.params:
+            self.params = params
+            if self.graph is not None:
+                # eager once: another K' is another kernel, whose first launch is not one under capture.  It writes the
+                # search state as the last decode left it; begin() resets all of it before it is used again
+                self._select()
+                self._capture()
+
+    def _reset(self):
+        super()._reset()
+        Kp = self.K // self.params[0]
+        self.scores.view(self.B, self.K)[:, ::Kp] = 0.0
+        self.finished.view(self.B, self.K)[:, ::Kp] = 0
+
+    def _select(self):
+        V = self.logp.shape[-1]
+        ops.group_beam_select(self.logp, V, self.scores, self.finished, self.parent, self.tok, self.out, self.t, self.last_live,
+                              self.B, self.K, V, self.end_idx, self.pad_idx, *self.params)
+
+    def _choose(self, logp):
+        self._select()
+        for phase in (0, 1):
+            ops.beam_reorder(self._table, self._n_buffers, self._n_blocks, self.parent, self.R, self.K, self.t, phase)
 
 
 # ------------------------------------------------------------------------------------------------------------- sampling

@@ -796,6 +796,35 @@ def beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_live, B, 
                                              pad_idx, stream()), "bmhrl_beam_select")
 
 
+def group_beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_live, B, K, V, end_idx, pad_idx, G,
+                      diversity_penalty, scores_out=None, finished_out=None):
+    """beam_select for diverse beam search (csrc/group_beam.hip; rules G2-G4 of decode.py, see bmhrl_group_beam_select in
+    include/bmhrl_hip.h): the K beams of a sample form G groups of K / G that choose one after another, a later group paying
+    diversity_penalty per earlier beam that chose the token.  Buffers and outputs as beam_select's."""
+    _need_cuda(logp, scores, finished, parent, tok, hist, t, last_live)
+    scores_out = scores if scores_out is None else scores_out
+    finished_out = finished if finished_out is None else finished_out
+    R = B * K
+    lam = float(diversity_penalty)
+    if not (1 <= K <= BEAM_MAX and G >= 1 and K % G == 0 and K // G <= V and ld >= V and logp.dtype == torch.float32
+            and logp.numel() >= (R - 1) * ld + V):
+        raise ValueError("group_beam_select: need 1 <= K <= 16, G >= 1 dividing K, K / G <= V and fp32 logp rows (B*K, ld >= V)")
+    if not (lam >= 0 and lam < float("inf")):
+        raise ValueError(f"group_beam_select: diversity_penalty must be finite and >= 0, got {diversity_penalty}")
+    for x, dt in ((scores, torch.float32), (scores_out, torch.float32), (finished, torch.uint8), (finished_out, torch.uint8),
+                  (parent, torch.int32), (tok, torch.int64)):
+        if x.dtype != dt or x.numel() < R or not x.is_contiguous():
+            raise ValueError(f"group_beam_select: expected a contiguous {dt} buffer of {R} elements")
+    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != R or hist.stride(1) != 1:
+        raise ValueError("group_beam_select: hist must be (B*K, cols) int64 with contiguous rows")
+    if t.dtype != torch.int64 or last_live.dtype != torch.int32:
+        raise ValueError("group_beam_select: t is an int64 word, last_live an int32 word")
+    _lib.check(_lib.load().bmhrl_group_beam_select(
+        logp.data_ptr(), ld, scores.data_ptr(), finished.data_ptr(), scores_out.data_ptr(), finished_out.data_ptr(),
+        parent.data_ptr(), tok.data_ptr(), hist.data_ptr(), hist.stride(0), hist.shape[1], t.data_ptr(), last_live.data_ptr(),
+        B, K, V, end_idx, pad_idx, G, lam, stream()), "bmhrl_group_beam_select")
+
+
 def beam_reorder_table(buffers, rows, device):
     """[(state, scratch, pos_bytes)] -> (device table of bmhrl_beam_buffer entries, n_blocks) for beam_reorder.  state and
     scratch: contiguous tensors of the same shape whose first axis is the beam row; pos_bytes: bytes of one position of a

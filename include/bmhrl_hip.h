@@ -647,6 +647,28 @@ int bmhrl_beam_reorder(const bmhrl_beam_buffer* table, int32_t n_buffers, int64_
                        int32_t rows, int32_t K, const int64_t* t, int32_t phase, bmhrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Diverse (group) beam search (bmhrl_amd/decode.py GroupBeamDecoder, rules G1-G4 of its group beam search section).
+ *  bmhrl_group_beam_select: bmhrl_beam_select with the K beams of a sample split into G groups of K' = K / G consecutive
+ *    beams that choose one after another, g = 0 .. G-1.  A live beam k of group g offers (k, v) with s = score_k + logp[k][v]
+ *    and the selection value a = s - diversity_penalty * c (c as fp32, one fp32 multiply, one fp32 subtract, no FMA; c = 0:
+ *    a = s bit for bit), c = how many beams of groups 0 .. g-1 of the sample chose, at this step, token v as a candidate of
+ *    a live beam; a finished beam offers (k, pad) with a = s = score_k, neither penalised nor counted.  The K' best of the
+ *    group's candidates by a, ties to the smaller k*V + v, become beams g*K' .. g*K' + K' - 1 best first: a parent always
+ *    lies in its own group.  The new score is s, never a.  Outputs exactly as bmhrl_beam_select writes them (scores and
+ *    flags may alias the inputs; parent = the beam index 0..K-1 within the sample; the next token; hist[row][t + 1] when
+ *    t + 1 < hist_cols; last_live[0] = t + 1 when any new beam is live); t is read from the device word.  One launch for
+ *    all groups; G = 1 selects what bmhrl_beam_select selects, bit for bit.
+ *    Refused with -22, outputs untouched: a null pointer, B < 1, K < 1, K > 16, G < 1, K % G != 0, K / G > V, a
+ *    diversity_penalty that is negative or not finite (and the ld / ldh / hist_cols / pad_idx conditions of
+ *    bmhrl_beam_select).
+ * ------------------------------------------------------------------------------------------- */
+int bmhrl_group_beam_select(const float* logp, int64_t ld, const float* scores_in, const uint8_t* finished_in,
+                            float* scores_out, uint8_t* finished_out, int32_t* parent, int64_t* tok, int64_t* hist,
+                            int64_t ldh, int32_t hist_cols, const int64_t* t, int32_t* last_live, int32_t B, int32_t K,
+                            int32_t V, int32_t end_idx, int32_t pad_idx, int32_t G, float diversity_penalty,
+                            bmhrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Per-prefix caption rewards (bmhrl_amd/rewards.py CiderScorer / BleuScorer): the score of every prefix of every sampled
  * caption against its reference caption, as the reference's metrics/cider.py and metrics/bleu.py compute it on the host.
  *  hyp (B, L) int64 vocab ids, row stride ldh; vmap[V]: vocab id -> word id (-1: the token yields no word; ids outside
