@@ -141,6 +141,7 @@ PROTOTYPES = {
                       ptr],
     "bmhrl_meteor": [ptr, i64, ptr, ptr, i32, ptr, ptr, i32, ptr, ptr, i64, ptr, f64, f64, f64, i32, i32, i32, ptr, i64, ptr,
                      i64, ptr],
+    "bmhrl_caption_eval": [ptr, i64, ptr, ptr, i64, ptr, ptr, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr],
     "bmhrl_sample_step": [ptr, i64, i32, i32, f32, i32, f32, u64, ptr, ptr, i64, i32, i32, ptr, ptr, ptr, i64, ptr, ptr, ptr, ptr],
     "bmhrl_logit_rules": [ptr, i64, i32, i32, ptr, i64, ptr, i32, i32, f32, i32, i32, ptr],
     "bmhrl_consensus": [ptr, i64, i32, i32, i32, i64, i32, ptr, i32, ptr, ptr, ptr],

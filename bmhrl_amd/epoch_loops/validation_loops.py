@@ -4,9 +4,9 @@ validation pass and the next-word loss pass, with the reference's signatures and
 validation_1by1_loop (:13-137) is where the decoder spends its time: every batch is decoded token by token.  Here the
 decoder is bmhrl_amd.decode (per-clip memory K|V, incremental caption K|V cache, one HIP graph per token); the host side --
 ids -> words, cut at </s>, capitalise, the ActivityNet-captions result dictionary and its JSON file -- keeps the reference's
-format so that its evaluator reads the file unchanged.  The evaluator itself (evaluation/evaluate.py: Java METEOR, PTB
-tokenizer) is outside the hot path: it is imported from the reference when that is on sys.path, otherwise the loop returns
-after writing the predictions."""
+format so that its evaluator reads the file unchanged.  The file is scored by the reference's evaluator
+(evaluation/evaluate.py: Java METEOR, PTB tokenizer) when that is on sys.path -- otherwise the loop returns after writing
+the predictions -- or, with evaluator="device" / cfg.caption_evaluator = "device", by bmhrl_amd.evaluate on the device."""
 import contextlib
 import io
 import json
@@ -58,26 +58,41 @@ def predict_1by1(cfg, model, loader, decoder):
     return predictions
 
 
-def calculate_metrics(reference_paths, submission_path, tIoUs, max_prop_per_vid, verbose=True, only_proposals=False):
-    """per-tIoU and averaged scores of the reference's ANETcaptions evaluator (:160-183); needs the reference's
-    evaluation package (and its Java METEOR) on sys.path -- not part of this package"""
-    try:
-        from evaluation.evaluate import ANETcaptions
-    except Exception as e:  # noqa: BLE001
-        raise NotImplementedError("the caption evaluator (evaluation/evaluate.py of the reference: PTB tokenizer, METEOR jar) is "
-                                  "outside the hot path this package replaces; put the reference on sys.path to score") from e
-    ev = ANETcaptions(reference_paths, submission_path, tIoUs, max_prop_per_vid, ["results", "version", "external_data"],
-                      verbose, only_proposals)
+def calculate_metrics(reference_paths, submission_path, tIoUs, max_prop_per_vid, verbose=True, only_proposals=False,
+                      evaluator=None, evaluator_options=None):
+    """per-tIoU and averaged scores (:160-183).  evaluator None: the reference's ANETcaptions, which needs the reference's
+    evaluation package (and its Java METEOR) on sys.path -- not part of this package.  evaluator "device": this package's
+    bmhrl_amd.evaluate.DenseCaptionEvaluator (what its METEOR and tokenizer are: see there), with evaluator_options as its
+    keywords (device, tokenizer, stemmer, synonyms)."""
+    fields = ["results", "version", "external_data"]
+    if evaluator is None:
+        try:
+            from evaluation.evaluate import ANETcaptions
+        except Exception as e:  # noqa: BLE001
+            raise NotImplementedError("the reference's caption evaluator (evaluation/evaluate.py: PTB tokenizer, METEOR jar) is "
+                                      "not importable; put the reference on sys.path, or score on the device with "
+                                      "evaluator='device' (cfg.caption_evaluator)") from e
+        ev = ANETcaptions(reference_paths, submission_path, tIoUs, max_prop_per_vid, fields, verbose, only_proposals)
+    elif evaluator == "device":
+        from ..evaluate import DenseCaptionEvaluator
+        ev = DenseCaptionEvaluator(reference_paths, submission_path, tIoUs, max_prop_per_vid, fields, verbose, only_proposals,
+                                   **(evaluator_options or {}))
+    else:
+        raise ValueError(f"unknown caption evaluator {evaluator!r} (None: the reference's, 'device': this package's)")
     ev.evaluate()
     metrics = {tiou: {name: scores[i] for name, scores in ev.scores.items()} for i, tiou in enumerate(tIoUs)}
     metrics["Average across tIoUs"] = {name: sum(scores) / float(len(scores)) for name, scores in ev.scores.items()}
     return metrics
 
 
-def validation_1by1_loop(cfg, model, loader, decoder, epoch, TBoard):
+def validation_1by1_loop(cfg, model, loader, decoder, epoch, TBoard, evaluator=None):
     """Greedy-decode the whole loader, write captioning_results_<phase>_e<epoch>.json under cfg.log_path and score it.
     Returns the metrics dictionary; None when cfg.log_path is None (as the reference); the predictions dictionary when the
-    evaluator is not importable (see calculate_metrics)."""
+    evaluator is not importable (see calculate_metrics).  evaluator: None takes cfg.caption_evaluator when the config has
+    one (the reference's driver passes six positional arguments), and None there too scores with the reference's
+    evaluator; "device" scores with bmhrl_amd.evaluate (keywords: cfg.caption_evaluator_options, a dict)."""
+    if evaluator is None:
+        evaluator = getattr(cfg, "caption_evaluator", None)
     t_start = time()
     model.eval()
     loader.dataset.update_iterator()
@@ -94,7 +109,8 @@ def validation_1by1_loop(cfg, model, loader, decoder, epoch, TBoard):
         json.dump(predictions, f)
     try:
         with contextlib.redirect_stdout(io.StringIO()):
-            val_metrics = calculate_metrics(reference_paths, path, tIoUs, cfg.max_prop_per_vid)
+            val_metrics = calculate_metrics(reference_paths, path, tIoUs, cfg.max_prop_per_vid, evaluator=evaluator,
+                                            evaluator_options=getattr(cfg, "caption_evaluator_options", None))
     except NotImplementedError:
         predictions["submission_path"] = path
         return predictions

@@ -1,0 +1,339 @@
+"""Dense-captioning evaluator on the device: the reference's evaluation/evaluate.py ANETcaptions (tIoU pairing, Bleu_1..4,
+METEOR, ROUGE_L, CIDEr per video, detection precision / recall) without the Java PTB tokenizer, the METEOR jar or a
+pycocoevalcap checkout.  DESIGN.md section 24 has the rules and the measurements.
+
+The host pairs predictions with ground-truth captions (pair_captions), tokenizes every distinct sentence once, maps the
+tokens to ids of one rewards.StringTable and hands the pairs of all videos, grouped per video, to one call of
+ops.caption_eval (csrc/caption_eval.hip): BLEU over the video's pairs, mean ROUGE-L, mean CIDEr with the document
+frequencies of those same pairs.  METEOR goes through the per-prefix reward launch (ops.meteor) and
+reads the score of the whole hypothesis.
+
+What is and is not the published protocol: `Bleu_*`, `ROUGE_L`, `CIDEr`, `Precision` and `Recall` are the pycocoevalcap /
+evaluate.py functions of the tokens they are given.  `tokenize` is a stand-in for the Java PTB tokenizer (lowercase, words
+split from punctuation, pycocoevalcap's punctuation tokens dropped), not that tokenizer; pass tokenizer= to use tokens
+of your own.  `METEOR` is the nltk-3.5 formula (exact, stem, synonym stages; alpha 0.9, beta 3, gamma 0.5), the mean over
+a video's pairs of the whole-hypothesis score -- not Java METEOR 1.5, which has other stages and weights and reports one
+corpus aggregate per call.  It is comparable between runs of this package, not to published METEOR figures.
+"""
+from __future__ import annotations
+
+import json
+import re
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+PREDICTION_FIELDS = ("results", "version", "external_data")
+METRICS = ("Bleu_1", "Bleu_2", "Bleu_3", "Bleu_4", "METEOR", "ROUGE_L", "CIDEr")
+# the tokens pycocoevalcap's tokenizer drops
+PUNCTUATIONS = frozenset(["''", "'", "``", "`", "-LRB-", "-RRB-", "-LCB-", "-RCB-", ".", "?", "!", ",", ":", "-", "--", "...",
+                          ";"])
+# the one word of the reference a prediction without an overlap is scored against: not ASCII, so no sentence that passed
+# remove_nonascii holds it
+GARBAGE = "␀"
+_TOKEN = re.compile(r"\.\.\.|--|\w+|[^\w\s]", re.ASCII)
+_METEOR_CHUNK = 32768                         # pairs per METEOR launch (bounds the (pairs, L) score rows)
+
+
+def remove_nonascii(text: str) -> str:
+    return "".join(c if ord(c) < 128 else " " for c in text)
+
+
+def tokenize(sentence: str) -> List[str]:
+    """Stand-in for the Java PTB tokenizer: lowercase, runs of letters / digits / "_" are words, every other non-space
+    character is a token of its own ("..." and "--" stay whole), pycocoevalcap's punctuation tokens are dropped.  An
+    empty or punctuation-only sentence gives []."""
+    return [t for t in _TOKEN.findall(sentence.lower()) if t not in PUNCTUATIONS]
+
+
+def tiou(interval_1: Sequence[float], interval_2: Sequence[float]) -> float:
+    """temporal intersection over union as evaluate.py computes it (the union is capped by the sum of the two lengths)"""
+    start_i, end_i = interval_1[0], interval_1[1]
+    start, end = interval_2[0], interval_2[1]
+    intersection = max(0, min(end, end_i) - max(start, start_i))
+    union = min(max(end, end_i) - min(start, start_i), end - start + end_i - start_i)
+    return float(intersection) / (union + 1e-8)
+
+
+def ground_truth_video_ids(ground_truths: Sequence[dict]) -> List[str]:
+    """the union of the files' video ids, sorted"""
+    return sorted(set().union(*[set(gt.keys()) for gt in ground_truths]))
+
+
+def pair_captions(ground_truths: Sequence[dict], prediction: Dict[str, list], tiou_threshold: float
+                  ) -> Dict[str, List[Tuple[str, Optional[str]]]]:
+    """video id -> [(predicted sentence, ground-truth sentence)] for every ground-truth video id (sorted).  A prediction
+    pairs with every caption of every ground-truth file whose tIoU is >= the threshold, in the order prediction, file,
+    caption; a prediction that pairs with nothing gives one pair whose ground-truth sentence is None (scored against a
+    reference no hypothesis shares a word with).  Sentences have passed remove_nonascii.  Videos without predictions
+    get []; videos that only the prediction holds are left out."""
+    out: Dict[str, List[Tuple[str, Optional[str]]]] = {}
+    for vid in ground_truth_video_ids(ground_truths):
+        pairs = out[vid] = []
+        for pred in prediction.get(vid, ()):
+            hyp = remove_nonascii(pred["sentence"])
+            added = False
+            for gt in ground_truths:
+                if vid not in gt:
+                    continue
+                caps = gt[vid]
+                for idx, stamp in enumerate(caps["timestamps"]):
+                    if tiou(pred["timestamp"], stamp) >= tiou_threshold:
+                        pairs.append((hyp, remove_nonascii(caps["sentences"][idx])))
+                        added = True
+            if not added:
+                pairs.append((hyp, None))
+    return out
+
+
+def detection_scores(ground_truths: Sequence[dict], prediction: Dict[str, list], tiou_threshold: float
+                     ) -> Tuple[float, float]:
+    """(precision, recall) of the predicted segments as evaluate.py's evaluate_detection: per video and file, a
+    prediction / a ground-truth segment is covered when some tIoU is > the threshold (strictly); the best value over
+    the files; the mean over the ground-truth videos.  A video without predictions (none, or an empty list) counts
+    precision 0."""
+    vids = ground_truth_video_ids(ground_truths)
+    precision, recall = [], []
+    for vid in vids:
+        best_p = best_r = 0.0
+        preds = prediction.get(vid, ())
+        for gt in ground_truths:
+            if vid not in gt:
+                continue
+            stamps = gt[vid]["timestamps"]
+            refs_hit, preds_hit = set(), set()
+            for pi, pred in enumerate(preds):
+                for ri, stamp in enumerate(stamps):
+                    if tiou(pred["timestamp"], stamp) > tiou_threshold:
+                        refs_hit.add(ri)
+                        preds_hit.add(pi)
+            if len(preds):
+                best_p = max(best_p, float(len(preds_hit)) / len(preds))
+            best_r = max(best_r, float(len(refs_hit)) / len(stamps))
+        precision.append(best_p)
+        recall.append(best_r)
+    return sum(precision) / len(precision), sum(recall) / len(recall)
+
+
+def _load(x):
+    if isinstance(x, dict):
+        return x
+    with open(x) as f:
+        return json.load(f)
+
+
+class DenseCaptionEvaluator:
+    """ANETcaptions of the reference's evaluation/evaluate.py: the same positional arguments, .evaluate() and .scores (a
+    dict of lists, one entry per tIoU: Bleu_1..4, METEOR, ROUGE_L, CIDEr, and with verbose or only_proposals also Recall
+    and Precision).  A ground-truth entry or the prediction may be an already loaded dict instead of a path.
+    tokenizer: sentence -> list of words (default: tokenize).  stemmer / synonyms: as rewards.MeteorTables takes them
+    (None: nltk's, an ImportError naming the two keywords when nltk is missing; False: the stage is off)."""
+
+    def __init__(self, ground_truth_filenames=None, prediction_filename=None, tious=None, max_proposals=1000,
+                 prediction_fields=PREDICTION_FIELDS, verbose=False, only_proposals=False, *, device="cuda",
+                 tokenizer: Callable[[str], List[str]] = tokenize, stemmer=None, synonyms=None):
+        if tious is None or len(tious) == 0:
+            raise IOError("Please input a valid tIoU.")
+        if not ground_truth_filenames:
+            raise IOError("Please input a valid ground truth file.")
+        if not prediction_filename:
+            raise IOError("Please input a valid prediction file.")
+        self.only_proposals = only_proposals
+        self.verbose = verbose
+        self.tious = tious
+        self.max_proposals = max_proposals
+        self.pred_fields = prediction_fields
+        self.device = device
+        self.tokenizer = tokenizer
+        self._stemmer, self._synonyms = stemmer, synonyms
+        self.ground_truths = self.import_ground_truths(ground_truth_filenames)
+        self.prediction = self.import_prediction(prediction_filename)
+        self._tokens: Dict[str, Tuple[str, ...]] = {}
+        self._meteor_tables = None
+        self.scores: Dict[str, list] = {}
+        if not only_proposals:
+            self.meteor_tables()              # a missing stemmer / synonym source is reported here, not after the pairing
+
+    # ---- loading
+    def import_prediction(self, prediction_filename) -> Dict[str, list]:
+        if self.verbose:
+            print("| Loading submission...")
+        try:
+            submission = _load(prediction_filename)
+        except OSError as e:
+            raise IOError(f"Please input a valid prediction file. ({e})") from e
+        if not all(field in submission.keys() for field in self.pred_fields):
+            raise IOError("Please input a valid ground truth file.")
+        return {vid: segs[:self.max_proposals] for vid, segs in submission["results"].items()}
+
+    def import_ground_truths(self, filenames) -> List[dict]:
+        if isinstance(filenames, (str, dict)):
+            filenames = [filenames]
+        gts = []
+        self.n_ref_vids = set()
+        for filename in filenames:
+            try:
+                gt = _load(filename)
+            except OSError as e:
+                raise IOError(f"Please input a valid ground truth file. ({e})") from e
+            self.n_ref_vids.update(gt.keys())
+            gts.append(gt)
+        if self.verbose:
+            print("| Loading GT. #files: %d, #videos: %d" % (len(gts), len(self.n_ref_vids)))
+        return gts
+
+    def get_gt_vid_ids(self) -> List[str]:
+        return ground_truth_video_ids(self.ground_truths)
+
+    # ---- scoring
+    def evaluate(self) -> None:
+        self.scores = {}
+        if not self.only_proposals:
+            for t in self.tious:
+                for metric, score in self.evaluate_tiou(t).items():
+                    self.scores.setdefault(metric, []).append(score)
+        if self.verbose:
+            self.scores["Recall"], self.scores["Precision"] = [], []
+            for t in self.tious:
+                precision, recall = self.evaluate_detection(t)
+                self.scores["Recall"].append(recall)
+                self.scores["Precision"].append(precision)
+
+    def evaluate_detection(self, tiou_threshold) -> Tuple[float, float]:
+        return detection_scores(self.ground_truths, self.prediction, tiou_threshold)
+
+    def _tok(self, sentence: str) -> Tuple[str, ...]:
+        t = self._tokens.get(sentence)
+        if t is None:
+            t = self._tokens[sentence] = tuple(self.tokenizer(sentence))
+        return t
+
+    def tokenized_pairs(self, tiou_threshold):
+        """(video ids, group_off, hypothesis token tuples, reference token tuples) of a threshold's pairs; the groups are
+        the ground-truth videos in sorted order, those without a pair included (empty)"""
+        paired = pair_captions(self.ground_truths, self.prediction, tiou_threshold)
+        vids = list(paired)
+        off = [0]
+        hyps, refs = [], []
+        for vid in vids:
+            for hyp, ref in paired[vid]:
+                hyps.append(self._tok(hyp))
+                refs.append((GARBAGE,) if ref is None else self._tok(ref))
+            off.append(len(hyps))
+        return vids, off, hyps, refs
+
+    def evaluate_tiou(self, tiou_threshold) -> Dict[str, float]:
+        vids, off, hyps, refs = self.tokenized_pairs(tiou_threshold)
+        if not hyps:                           # nothing was predicted for any ground-truth video: every video scores 0
+            return {m: 0.0 for m in METRICS}
+        per_video = score_pairs(hyps, refs, off, self.device, self.meteor_tables())
+        out = {m: float(np.mean(per_video[m])) for m in METRICS}
+        if self.verbose:
+            for m in METRICS:
+                print("Calculated tIoU: %1.1f, %s: %0.3f" % (tiou_threshold, m, out[m]))
+        return out
+
+    def meteor_tables(self):
+        """rewards.MeteorTables over the distinct hypothesis words of the submission (built at first use)"""
+        if self._meteor_tables is None:
+            from .rewards import MeteorTables
+            words: Dict[str, None] = {}
+            for vid in sorted(self.prediction):
+                for seg in self.prediction[vid]:
+                    for w in self._tok(remove_nonascii(seg["sentence"])):
+                        words.setdefault(w.lower())
+            self._meteor_tables = MeteorTables(list(words), self._stemmer, self._synonyms)
+        return self._meteor_tables
+
+
+def _distinct(seqs: Sequence[Sequence[str]]):
+    """(the distinct token tuples in order of first appearance, (len(seqs),) int64 index of every sequence among them)"""
+    index: Dict[Tuple[str, ...], int] = {}
+    idx = np.empty(len(seqs), dtype=np.int64)
+    for p, s in enumerate(seqs):
+        idx[p] = index.setdefault(tuple(s), len(index))
+    return list(index), idx
+
+
+def _rows(sents, ids_of, dtype, fill):
+    """(n, max(1, longest)) matrix of ids_of(sentence), padded with fill, and the (n,) lengths"""
+    lens = np.array([len(s) for s in sents], dtype=np.int64)
+    out = np.full((len(sents), max(1, int(lens.max()))), fill, dtype=dtype)
+    for i, s in enumerate(sents):
+        out[i, :len(s)] = ids_of(s)
+    return out, lens
+
+
+def encode_pairs(hyps: Sequence[Sequence[str]], refs: Sequence[Sequence[str]]):
+    """word ids of one rewards.StringTable over every token of the call: hyp (P, L) / ref (P, R) int32 (zero padded, L and
+    R at least 1) and their lengths.  Every distinct sentence is encoded once."""
+    from . import ops
+    from .rewards import StringTable
+    table = StringTable()
+    (hs, hi), (rs, ri) = _distinct(hyps), _distinct(refs)
+    ids_of = lambda s: [table.add(w) for w in s]                                                          # noqa: E731
+    (wh, lh), (wr, lr) = _rows(hs, ids_of, np.int32, 0), _rows(rs, ids_of, np.int32, 0)
+    if wh.shape[1] > ops.REWARDS_MAX_L or wr.shape[1] > ops.REWARDS_MAX_R:
+        raise ValueError(f"a sentence of {wh.shape[1]} / a reference of {wr.shape[1]} tokens; at most {ops.REWARDS_MAX_L} / "
+                         f"{ops.REWARDS_MAX_R} are supported")
+    return wh[hi], lh[hi].astype(np.int32), wr[ri], lr[ri].astype(np.int32)
+
+
+def meteor_pairs(hyps: Sequence[Sequence[str]], refs: Sequence[Sequence[str]], tables, device) -> np.ndarray:
+    """(P,) fp64: the METEOR score of every whole hypothesis against its reference, through the per-prefix launch
+    (ops.meteor): the pair's score is the row's column hyp_len - 1; an empty hypothesis scores 0.  `tables`: a
+    rewards.MeteorTables whose vocabulary holds every hypothesis word."""
+    import torch
+    from . import ops
+    from .rewards import MeteorScorer
+    P = len(hyps)
+    out = np.zeros(P, dtype=np.float64)
+    word_vocab = {}
+    for v, wid in enumerate(tables.vmap):      # word id -> a vocab id that yields it
+        if wid >= 0:
+            word_vocab.setdefault(int(wid), v)
+    (hs, hi), (rs, ri) = _distinct(hyps), _distinct(refs)
+    ref_w, ref_s = tables.encode([" ".join(r) for r in rs])
+    # hypothesis rows of vocab ids (-1: outside the vocabulary, yields no word); reference rows of word and stem ids
+    wh, lh = _rows(hs, lambda s: [word_vocab[tables.strings[w.lower()]] for w in s], np.int64, -1)
+    ww, lr = _rows(ref_w, lambda s: s, np.int32, 0)
+    ws, _ = _rows(ref_s, lambda s: s, np.int32, 0)
+    if wh.shape[1] > ops.REWARDS_MAX_L:
+        raise ValueError(f"a sentence of {wh.shape[1]} tokens; at most {ops.REWARDS_MAX_L} are supported")
+    dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device)          # noqa: E731
+    vmap, vstem, syn_off, syn_ids = dev(tables.vmap), dev(tables.vstem), dev(tables.syn_off), dev(tables.syn_ids)
+    for lo in range(0, P, _METEOR_CHUNK):
+        h, r = hi[lo:lo + _METEOR_CHUNK], ri[lo:lo + _METEOR_CHUNK]
+        B, L, R = len(h), max(1, int(lh[h].max())), max(1, int(lr[r].max()))
+        hyp_len = lh[h]
+        hyp_d, ref_d, stem_d = dev(wh[h, :L]), dev(ww[r, :R]), dev(ws[r, :R])
+        scores = torch.empty(B, L, dtype=torch.float64, device=device)
+        delta = torch.empty(B, L, dtype=torch.float32, device=device)
+        ops.meteor(hyp_d, vmap, vstem, syn_off, syn_ids, ref_d, stem_d if vstem is not None else None,
+                   dev(lr[r].astype(np.int32)), MeteorScorer.alpha, MeteorScorer.beta, MeteorScorer.gamma_frag, scores, delta)
+        whole = scores.gather(1, dev(np.maximum(hyp_len - 1, 0))[:, None])[:, 0].cpu().numpy()
+        out[lo:lo + B] = np.where(hyp_len > 0, whole, 0.0)
+    return out
+
+
+def score_pairs(hyps, refs, group_off: Sequence[int], device, tables) -> Dict[str, np.ndarray]:
+    """per-group values of the seven metrics, (G,) fp64 each, of the pairs hyps[p] / refs[p] (token sequences) grouped by
+    group_off (G + 1, ascending from 0 to the number of pairs; an empty group scores 0).  One caption_eval call and the
+    METEOR launches; at least one pair."""
+    import torch
+    from . import ops
+    hyp, hyp_len, ref, ref_len = encode_pairs(hyps, refs)
+    off = np.asarray(group_off, dtype=np.int32)
+    dev = lambda a: torch.from_numpy(a).to(device)                                                         # noqa: E731
+    _, _, _, group_scores = ops.caption_eval(dev(hyp), dev(hyp_len), dev(ref), dev(ref_len), dev(off))
+    meteor = meteor_pairs(hyps, refs, tables, device)
+    gs = group_scores.cpu().numpy()
+    counts = np.diff(off)
+    sums = np.zeros(len(counts), dtype=np.float64)
+    for g in np.nonzero(counts)[0]:            # pair order within a group
+        sums[g] = sum(meteor[off[g]:off[g + 1]].tolist())
+    out = {f"Bleu_{k + 1}": gs[:, k].copy() for k in range(4)}
+    out["METEOR"] = sums / np.maximum(counts, 1)
+    out["ROUGE_L"] = gs[:, 4].copy()
+    out["CIDEr"] = gs[:, 5].copy()
+    return out

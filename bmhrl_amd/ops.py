@@ -925,8 +925,42 @@ def meteor(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, alpha, be
                                         delta.data_ptr(), delta.stride(0), stream()), "bmhrl_meteor")
 
 
+# ---- evaluation forms of the caption metrics (csrc/caption_eval.hip)
+CAPTION_EVAL_PAIR_INTS, CAPTION_EVAL_GROUP_SCORES = 10, 6      # BMHRL_CAPTION_EVAL_* of include/bmhrl_hip.h
+
+
+def caption_eval(hyp, hyp_len, ref, ref_len, group_off):
+    """BLEU counts, LCS length and CIDEr of P (hypothesis, reference) pairs and Bleu_1..4 / mean ROUGE_L / mean CIDEr of
+    the G groups of contiguous pairs group_off (G + 1) int32 delimits; see bmhrl_caption_eval in include/bmhrl_hip.h.
+    hyp (P, L) / ref (P, R) int32 word ids with contiguous rows, hyp_len / ref_len (P) int32.  Returns pair_ints (P, 10)
+    int32, pair_lcs (P) int32, pair_cider (P) fp64, group_scores (G, 6) fp64.  Synchronises the stream once (the offsets
+    are checked on the host); not for captured graphs."""
+    _need_cuda(hyp, hyp_len, ref, ref_len, group_off)
+    for t in (hyp, hyp_len, ref, ref_len, group_off):
+        if t.dtype != torch.int32:
+            raise ValueError("caption_eval: int32 tensors expected")
+    if hyp.dim() != 2 or ref.dim() != 2 or hyp.stride(1) != 1 or ref.stride(1) != 1 or ref.shape[0] != hyp.shape[0]:
+        raise ValueError("caption_eval: hyp (P, L) and ref (P, R) with contiguous rows expected")
+    P, L = hyp.shape
+    R = ref.shape[1]
+    G = group_off.numel() - 1
+    if hyp_len.numel() != P or ref_len.numel() != P or not hyp_len.is_contiguous() or not ref_len.is_contiguous() or \
+            not group_off.is_contiguous():
+        raise ValueError("caption_eval: hyp_len / ref_len (P) and group_off (G + 1), contiguous, expected")
+    dev = hyp.device
+    pair_ints = torch.empty(max(P, 0), CAPTION_EVAL_PAIR_INTS, dtype=torch.int32, device=dev)
+    pair_lcs = torch.empty(max(P, 0), dtype=torch.int32, device=dev)
+    pair_cider = torch.empty(max(P, 0), dtype=torch.float64, device=dev)
+    group_scores = torch.empty(max(G, 0), CAPTION_EVAL_GROUP_SCORES, dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().bmhrl_caption_eval(hyp.data_ptr(), hyp.stride(0), hyp_len.data_ptr(), ref.data_ptr(), ref.stride(0),
+                                              ref_len.data_ptr(), group_off.data_ptr(), P, G, L, R, pair_ints.data_ptr(),
+                                              pair_lcs.data_ptr(), pair_cider.data_ptr(), group_scores.data_ptr(), stream()),
+               "bmhrl_caption_eval")
+    return pair_ints, pair_lcs, pair_cider, group_scores
+
+
 # ---- sampled caption decoding (csrc/sample.hip)
-SAMPLE_MAX_V = 16384                          # BMHRL_SAMPLE_MAX_V of include/bmhrl_hip.h
+SAMPLE_MAX_V = 16384                         # BMHRL_SAMPLE_MAX_V of include/bmhrl_hip.h
 
 
 def sample_step(logp, ld, rows, V, temperature, top_k, top_p, seed, seed_dev, t, end_idx, pad_idx, finished, tok, out,

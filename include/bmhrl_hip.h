@@ -711,6 +711,32 @@ int bmhrl_meteor(const int64_t* hyp, int64_t ldh, const int32_t* vmap, const int
                  int32_t R, double* scores, int64_t lds, float* delta, int64_t ldd, bmhrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Evaluation forms of the caption metrics (bmhrl_amd/evaluate.py DenseCaptionEvaluator): what the
+ * reference's evaluation/evaluate.py asks of pycocoevalcap's Bleu, Rouge and Cider for each video, over the video's
+ * (prediction, reference) pairs.
+ *  hyp (P, L) / ref (P, R) int32 word ids >= 0 out of one string table, row strides ldh / ldr, of which hyp_len[p] /
+ *  ref_len[p] (device, clamped to [0, L] / [0, R]) are used.  group_off (G + 1) int32, device: the pairs
+ *  [group_off[g], group_off[g + 1]) are group g; group_off[0] = 0, group_off[G] = P, never descending (an empty group
+ *  scores 0 everywhere).  The offsets are copied back and checked before the launches, so the call synchronises the
+ *  stream once and cannot be captured in a graph; nothing is read back between the two launches.
+ *  Per pair: pair_ints (P, 10) int32 = BLEU's guess[4], clipped correct[4], the hypothesis length, the reference length;
+ *  pair_lcs (P) int32 the LCS length; pair_cider (P) fp64 = 10 * the mean over the gram lengths 1..4 of the tf-idf cosine
+ *  with the Gaussian length penalty (sigma 6, bigram counts), document frequency of a gram = the number of pairs of the
+ *  group whose reference holds it, log reference length = log(pairs of the group).
+ *  Per group: group_scores (G, 6) fp64 = Bleu_1..4 (counts and lengths summed over the group, tiny 1e-15, small 1e-9,
+ *  brevity penalty of the summed lengths), the mean ROUGE-L (beta 1.2; 0 for a pair without a common word), the mean of
+ *  pair_cider.  The floating-point sums run in pair order: two runs give equal bits.
+ *  L <= BMHRL_REWARDS_MAX_L, R <= BMHRL_REWARDS_MAX_R; null pointers, P <= 0, G <= 0, other shapes and offsets that
+ *  descend or do not span [0, P] are refused with -22.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_CAPTION_EVAL_PAIR_INTS 10
+#define BMHRL_CAPTION_EVAL_GROUP_SCORES 6
+int bmhrl_caption_eval(const int32_t* hyp, int64_t ldh, const int32_t* hyp_len, const int32_t* ref, int64_t ldr,
+                       const int32_t* ref_len, const int32_t* group_off, int32_t P, int32_t G, int32_t L, int32_t R,
+                       int32_t* pair_ints, int32_t* pair_lcs, double* pair_cider, double* group_scores,
+                       bmhrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sampled caption decoding (bmhrl_amd/decode.py SampleDecoder; the rules are at the top of its sampling section).  One step
  * for every row r of logp (rows, ld) fp32 log-probs, t read from the device word t[0]:
  *  finished[r] != 0: tok[r] = pad_idx, out[r][t + 1] = pad_idx, step_logp / step_logq [r][t] = 0, sum_logp unchanged;
