@@ -142,6 +142,9 @@ PROTOTYPES = {
     "bmhrl_meteor": [ptr, i64, ptr, ptr, i32, ptr, ptr, i32, ptr, ptr, i64, ptr, f64, f64, f64, i32, i32, i32, ptr, i64, ptr,
                      i64, ptr],
     "bmhrl_caption_eval": [ptr, i64, ptr, ptr, i64, ptr, ptr, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr],
+    "bmhrl_meteor_matrix": [ptr, i64, i32, i32, ptr, ptr, i32, ptr, ptr, i32, ptr, ptr, i64, ptr, i32, i32, ptr, i32, ptr, i32,
+                            ptr, ptr, ptr, i32, f64, f64, f64, ptr, i64, ptr],
+    "bmhrl_soda_dp": [ptr, i32, ptr, i32, ptr, ptr, ptr, i32, ptr, i64, ptr, i32, ptr, ptr],
     "bmhrl_sample_step": [ptr, i64, i32, i32, f32, i32, f32, u64, ptr, ptr, i64, i32, i32, ptr, ptr, ptr, i64, ptr, ptr, ptr, ptr],
     "bmhrl_logit_rules": [ptr, i64, i32, i32, ptr, i64, ptr, i32, i32, f32, i32, i32, ptr],
     "bmhrl_consensus": [ptr, i64, i32, i32, i32, i64, i32, ptr, i32, ptr, ptr, ptr],

@@ -14,12 +14,20 @@ split from punctuation, pycocoevalcap's punctuation tokens dropped), not that to
 of your own.  `METEOR` is the nltk-3.5 formula (exact, stem, synonym stages; alpha 0.9, beta 3, gamma 0.5), the mean over
 a video's pairs of the whole-hypothesis score -- not Java METEOR 1.5, which has other stages and weights and reports one
 corpus aggregate per call.  It is comparable between runs of this package, not to published METEOR figures.
+
+SODA_c (soda=True; soda_groups / soda_scores) is written from the paper (Fujita et al., "SODA: Story
+Oriented Dense Video Captioning Evaluation Framework", ECCV 2020), not from its authors' tool, which this package has never
+been compared with: per video and ground-truth file, the time-ordered one-to-one matching of predictions and references
+that maximises the sum of tIoU x METEOR (ops.meteor_matrix scores every prediction against every reference by index,
+ops.soda_dp runs the max-plus dynamic programme; csrc/soda.hip), its precision, recall and F1, the best file per video, the
+mean over the ground-truth videos.  Its METEOR is the function above, so the figure is comparable between runs of this
+package, not to published SODA_c.
 """
 from __future__ import annotations
 
 import json
 import re
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -33,6 +41,8 @@ PUNCTUATIONS = frozenset(["''", "'", "``", "`", "-LRB-", "-RRB-", "-LCB-", "-RCB
 GARBAGE = "␀"
 _TOKEN = re.compile(r"\.\.\.|--|\w+|[^\w\s]", re.ASCII)
 _METEOR_CHUNK = 32768                         # pairs per METEOR launch (bounds the (pairs, L) score rows)
+SODA_METRICS = ("SODA_c", "SODA_c_Precision", "SODA_c_Recall")
+_SODA_CELLS = 4 << 20                         # cells of the score matrices per pair of SODA launches (32 MiB of fp64)
 
 
 def remove_nonascii(text: str) -> str:
@@ -127,11 +137,15 @@ class DenseCaptionEvaluator:
     dict of lists, one entry per tIoU: Bleu_1..4, METEOR, ROUGE_L, CIDEr, and with verbose or only_proposals also Recall
     and Precision).  A ground-truth entry or the prediction may be an already loaded dict instead of a path.
     tokenizer: sentence -> list of words (default: tokenize).  stemmer / synonyms: as rewards.MeteorTables takes them
-    (None: nltk's, an ImportError naming the two keywords when nltk is missing; False: the stage is off)."""
+    (None: nltk's, an ImportError naming the two keywords when nltk is missing; False: the stage is off).
+    soda=True (and not only_proposals): .evaluate() also fills SODA_c, SODA_c_Precision and SODA_c_Recall, one entry per
+    tIoU, and .soda_per_video (video id -> [(precision, recall, F) per tIoU]); sort_references=True orders a video's
+    references by (start, end) like its predictions instead of keeping the file's order."""
 
     def __init__(self, ground_truth_filenames=None, prediction_filename=None, tious=None, max_proposals=1000,
                  prediction_fields=PREDICTION_FIELDS, verbose=False, only_proposals=False, *, device="cuda",
-                 tokenizer: Callable[[str], List[str]] = tokenize, stemmer=None, synonyms=None):
+                 tokenizer: Callable[[str], List[str]] = tokenize, stemmer=None, synonyms=None, soda=False,
+                 sort_references=False):
         if tious is None or len(tious) == 0:
             raise IOError("Please input a valid tIoU.")
         if not ground_truth_filenames:
@@ -146,6 +160,8 @@ class DenseCaptionEvaluator:
         self.device = device
         self.tokenizer = tokenizer
         self._stemmer, self._synonyms = stemmer, synonyms
+        self.soda, self.sort_references = bool(soda), bool(sort_references)
+        self.soda_per_video: Dict[str, List[Tuple[float, float, float]]] = {}
         self.ground_truths = self.import_ground_truths(ground_truth_filenames)
         self.prediction = self.import_prediction(prediction_filename)
         self._tokens: Dict[str, Tuple[str, ...]] = {}
@@ -192,6 +208,8 @@ class DenseCaptionEvaluator:
             for t in self.tious:
                 for metric, score in self.evaluate_tiou(t).items():
                     self.scores.setdefault(metric, []).append(score)
+            if self.soda:
+                self.scores.update(self.evaluate_soda())
         if self.verbose:
             self.scores["Recall"], self.scores["Precision"] = [], []
             for t in self.tious:
@@ -231,6 +249,18 @@ class DenseCaptionEvaluator:
         if self.verbose:
             for m in METRICS:
                 print("Calculated tIoU: %1.1f, %s: %0.3f" % (tiou_threshold, m, out[m]))
+        return out
+
+    def evaluate_soda(self) -> Dict[str, List[float]]:
+        """SODA_c, SODA_c_Precision, SODA_c_Recall per tIoU and .soda_per_video"""
+        groups, by_video = soda_groups(self.ground_truths, self.prediction, self.sort_references)
+        per_group = soda_scores(groups, self.tious, self.meteor_tables(), self.device, self._tok)
+        self.soda_per_video = soda_per_video(by_video, per_group, len(self.tious))
+        out = soda_means(self.soda_per_video, len(self.tious))
+        if self.verbose:
+            for k, t in enumerate(self.tious):
+                for m in SODA_METRICS:
+                    print("Calculated tIoU: %1.1f, %s: %0.3f" % (t, m, out[m][k]))
         return out
 
     def meteor_tables(self):
@@ -336,4 +366,173 @@ def score_pairs(hyps, refs, group_off: Sequence[int], device, tables) -> Dict[st
     out["METEOR"] = sums / np.maximum(counts, 1)
     out["ROUGE_L"] = gs[:, 4].copy()
     out["CIDEr"] = gs[:, 5].copy()
+    return out
+
+
+# ---- SODA_c
+class SodaGroup(NamedTuple):
+    """one (video, ground-truth file): the predictions in time order, the references in story order"""
+    video: str
+    file: int
+    pred_segments: List[Tuple[float, float]]
+    pred_sentences: List[str]
+    ref_segments: List[Tuple[float, float]]
+    ref_sentences: List[str]
+
+
+def _by_time(stamps) -> List[int]:
+    """the positions ordered by (start, end) ascending; ties keep their order"""
+    return sorted(range(len(stamps)), key=lambda k: (float(stamps[k][0]), float(stamps[k][1])))
+
+
+def soda_groups(ground_truths: Sequence[dict], prediction: Dict[str, list], sort_references: bool = False
+                ) -> Tuple[List[SodaGroup], Dict[str, List[int]]]:
+    """the host half of SODA_c: (groups, video id -> indices of its groups in file order) for every ground-truth video id
+    (sorted).  `prediction` is already cut to max_proposals per video.  A group exists for every file that holds the video
+    with at least one caption, when the video has a prediction; predictions are ordered by (start, end), stable;
+    references keep the file's order unless sort_references.  Sentences have passed remove_nonascii.  Videos that only the
+    prediction holds are left out."""
+    groups: List[SodaGroup] = []
+    by_video: Dict[str, List[int]] = {}
+    for vid in ground_truth_video_ids(ground_truths):
+        mine = by_video[vid] = []
+        preds = prediction.get(vid, ())
+        if not len(preds):
+            continue
+        order = _by_time([p["timestamp"] for p in preds])
+        segs = [(float(preds[k]["timestamp"][0]), float(preds[k]["timestamp"][1])) for k in order]
+        sents = [remove_nonascii(preds[k]["sentence"]) for k in order]
+        for f, gt in enumerate(ground_truths):
+            if vid not in gt or not len(gt[vid]["timestamps"]):
+                continue
+            stamps = gt[vid]["timestamps"]
+            rorder = _by_time(stamps) if sort_references else range(len(stamps))
+            mine.append(len(groups))
+            groups.append(SodaGroup(vid, f, segs, sents, [(float(stamps[k][0]), float(stamps[k][1])) for k in rorder],
+                                    [remove_nonascii(gt[vid]["sentences"][k]) for k in rorder]))
+    return groups, by_video
+
+
+def soda_encode(groups: Sequence[SodaGroup], tables, tokenizer: Callable[[str], Sequence[str]] = tokenize) -> dict:
+    """the distinct sentences of the groups as id rows (host): "hyp" (Nh, L) int64 vocab ids (-1 pads) with "hyp_len",
+    "ref" / "ref_stem" (Nr, R) int32 word / stem ids with "ref_len", and "members": per group the indices of its
+    hypotheses and of its references among them.  Every distinct sentence is tokenized and encoded once."""
+    from . import ops
+    tokens: Dict[str, Tuple[str, ...]] = {}
+
+    def tok(sentence):
+        t = tokens.get(sentence)
+        if t is None:
+            t = tokens[sentence] = tuple(tokenizer(sentence))
+        return t
+    hyp_index: Dict[Tuple[str, ...], int] = {}
+    ref_index: Dict[Tuple[str, ...], int] = {}
+    members = []                                # per group: indices of its hypotheses, of its references
+    for g in groups:
+        if len(g.ref_sentences) > ops.SODA_MAX_REFS:
+            raise ValueError(f"video {g.video}: {len(g.ref_sentences)} references in ground-truth file {g.file}; at most "
+                             f"{ops.SODA_MAX_REFS} are supported")
+        hs, rs = [tok(s) for s in g.pred_sentences], [tok(s) for s in g.ref_sentences]
+        if max(map(len, hs)) > ops.REWARDS_MAX_L or max(map(len, rs)) > ops.REWARDS_MAX_R:
+            raise ValueError(f"video {g.video}: a sentence of {max(map(len, hs))} / a reference of {max(map(len, rs))} "
+                             f"tokens; at most {ops.REWARDS_MAX_L} / {ops.REWARDS_MAX_R} are supported")
+        members.append((np.array([hyp_index.setdefault(h, len(hyp_index)) for h in hs], dtype=np.int32),
+                        np.array([ref_index.setdefault(r, len(ref_index)) for r in rs], dtype=np.int32)))
+    word_vocab = {}
+    for v, wid in enumerate(tables.vmap):      # word id -> a vocab id that yields it
+        if wid >= 0:
+            word_vocab.setdefault(int(wid), v)
+    ref_w, ref_s = tables.encode([" ".join(r) for r in ref_index])
+    wh, lh = _rows(list(hyp_index), lambda s: [word_vocab[tables.strings[w.lower()]] for w in s], np.int64, -1)
+    ww, lr = _rows(ref_w, lambda s: s, np.int32, 0)
+    ws, _ = _rows(ref_s, lambda s: s, np.int32, 0)
+    return {"hyp": wh, "hyp_len": lh, "ref": ww, "ref_stem": ws, "ref_len": lr.astype(np.int32), "members": members}
+
+
+def soda_chunks(groups: Sequence[SodaGroup], encoded: dict, max_cells: int = _SODA_CELLS):
+    """the groups in runs of at most max_cells cells (one group at least): yields (lo, hi, arrays) with the host operands
+    of the two launches for groups[lo:hi] -- hyp_idx, ref_idx, hyp_off, ref_off, cell_off, pred_seg, ref_seg -- and the
+    longest hypothesis "L" and reference "R" among them"""
+    members = encoded["members"]
+    off = lambda n, dt: np.concatenate([[0], np.cumsum(n)]).astype(dt)                                    # noqa: E731
+    lo = 0
+    while lo < len(groups):
+        hi, cells = lo, 0
+        while hi < len(groups) and (hi == lo or cells + len(members[hi][0]) * len(members[hi][1]) <= max_cells):
+            cells += len(members[hi][0]) * len(members[hi][1])
+            hi += 1
+        hyp_idx = np.concatenate([members[g][0] for g in range(lo, hi)])
+        ref_idx = np.concatenate([members[g][1] for g in range(lo, hi)])
+        P = np.array([len(members[g][0]) for g in range(lo, hi)], dtype=np.int64)
+        R = np.array([len(members[g][1]) for g in range(lo, hi)], dtype=np.int64)
+        yield lo, hi, {
+            "hyp_idx": hyp_idx, "ref_idx": ref_idx, "hyp_off": off(P, np.int32), "ref_off": off(R, np.int32),
+            "cell_off": off(P * R, np.int64),
+            "pred_seg": np.array([s for g in groups[lo:hi] for s in g.pred_segments], dtype=np.float64).reshape(-1, 2),
+            "ref_seg": np.array([s for g in groups[lo:hi] for s in g.ref_segments], dtype=np.float64).reshape(-1, 2),
+            "L": max(1, int(encoded["hyp_len"][hyp_idx].max())), "R": max(1, int(encoded["ref_len"][ref_idx].max()))}
+        lo = hi
+
+
+def soda_scores(groups: Sequence[SodaGroup], tious: Sequence[float], tables, device,
+                tokenizer: Callable[[str], Sequence[str]] = tokenize, max_cells: int = _SODA_CELLS) -> np.ndarray:
+    """the device half of SODA_c: (G, T, 4) fp64 max_score, precision, recall, F of every group at every tIoU.  Every
+    distinct sentence is tokenized and encoded once (soda_encode: references through tables.encode, hypotheses as vocab
+    ids, as meteor_pairs does); the groups go through ops.meteor_matrix and ops.soda_dp in chunks of about max_cells cells
+    (soda_chunks), the score matrices staying on the device.  `tables`: a rewards.MeteorTables whose vocabulary holds
+    every hypothesis word.  A video with more than ops.SODA_MAX_REFS references in a file, or a sentence past the METEOR
+    limits, is a ValueError."""
+    import torch
+    from . import ops
+    from .rewards import MeteorScorer
+    T = len(tious)
+    if not 1 <= T <= ops.SODA_MAX_T:
+        raise ValueError(f"{T} tIoU thresholds; between 1 and {ops.SODA_MAX_T} are supported")
+    out = np.zeros((len(groups), T, 4), dtype=np.float64)
+    if not len(groups):
+        return out
+    enc = soda_encode(groups, tables, tokenizer)
+    dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device)          # noqa: E731
+    vmap, vstem, syn_off, syn_ids = dev(tables.vmap), dev(tables.vstem), dev(tables.syn_off), dev(tables.syn_ids)
+    hyp_d, ref_d, len_d = dev(enc["hyp"]), dev(enc["ref"]), dev(enc["ref_len"])
+    stem_d = dev(enc["ref_stem"]) if vstem is not None else None
+    tious_d = dev(np.asarray(tious, dtype=np.float64))
+    for lo, hi, c in soda_chunks(groups, enc, max_cells):
+        L, R = c["L"], c["R"]
+        hyp_off, ref_off, cell_off = dev(c["hyp_off"]), dev(c["ref_off"]), dev(c["cell_off"])
+        S = torch.empty(int(c["cell_off"][-1]), dtype=torch.float64, device=device)
+        ops.meteor_matrix(hyp_d[:, :L], vmap, vstem, syn_off, syn_ids, ref_d[:, :R],
+                          stem_d[:, :R] if stem_d is not None else None, len_d, dev(c["hyp_idx"]), dev(c["ref_idx"]), hyp_off,
+                          ref_off, cell_off, MeteorScorer.alpha, MeteorScorer.beta, MeteorScorer.gamma_frag, S)
+        out[lo:hi] = ops.soda_dp(dev(c["pred_seg"]), dev(c["ref_seg"]), hyp_off, ref_off, cell_off, S, tious_d).cpu().numpy()
+    return out
+
+
+def soda_per_video(by_video: Dict[str, List[int]], per_group: np.ndarray, T: int
+                   ) -> Dict[str, List[Tuple[float, float, float]]]:
+    """video id -> [(precision, recall, F) per tIoU]: the triple of the file with the highest F, the first such file in
+    file order; (0, 0, 0) for a video without a group"""
+    out = {}
+    for vid, gs in by_video.items():
+        triples = []
+        for t in range(T):
+            best = (0.0, 0.0, 0.0)
+            for k, g in enumerate(gs):
+                p, r, f = (float(x) for x in per_group[g, t, 1:4])
+                if k == 0 or f > best[2]:
+                    best = (p, r, f)
+            triples.append(best)
+        out[vid] = triples
+    return out
+
+
+def soda_means(per_video: Dict[str, List[Tuple[float, float, float]]], T: int) -> Dict[str, List[float]]:
+    """the means over the videos (in their order) per tIoU: SODA_c is F, then precision and recall"""
+    out = {m: [] for m in SODA_METRICS}
+    for t in range(T):
+        for m, c in zip(SODA_METRICS, (2, 0, 1)):
+            total = 0.0
+            for triples in per_video.values():
+                total += triples[t][c]
+            out[m].append(total / len(per_video))
     return out

@@ -959,6 +959,82 @@ def caption_eval(hyp, hyp_len, ref, ref_len, group_off):
     return pair_ints, pair_lcs, pair_cider, group_scores
 
 
+# ---- SODA_c: the all-pairs METEOR matrix and the ordered assignment (csrc/soda.hip)
+SODA_MAX_REFS, SODA_MAX_T = 256, 16          # BMHRL_SODA_MAX_REFS / _T of include/bmhrl_hip.h
+
+
+def _soda_offsets(what, hyp_off, ref_off, cell_off):
+    if hyp_off.dtype != torch.int32 or ref_off.dtype != torch.int32 or cell_off.dtype != torch.int64:
+        raise ValueError(f"{what}: hyp_off / ref_off int32 and cell_off int64 expected")
+    G = hyp_off.numel() - 1
+    if ref_off.numel() != G + 1 or cell_off.numel() != G + 1 or not (hyp_off.is_contiguous() and ref_off.is_contiguous()
+                                                                     and cell_off.is_contiguous()):
+        raise ValueError(f"{what}: hyp_off, ref_off and cell_off (G + 1), contiguous, expected")
+    return G
+
+
+def meteor_matrix(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, hyp_idx, ref_idx, hyp_off, ref_off, cell_off,
+                  alpha, beta, gamma, S):
+    """whole-sentence METEOR of every (prediction, reference) cell of G groups into S (n_cells) fp64, group g row-major at
+    cell_off[g]; see bmhrl_meteor_matrix in include/bmhrl_hip.h.  hyp (Nh, L) int64 vocab ids and ref / ref_stem (Nr, R)
+    int32 with ref_len (Nr) int32 are the distinct sentences, hyp_idx (sum P) / ref_idx (sum R) int32 name the groups'
+    members, hyp_off / ref_off (G + 1) int32 and cell_off (G + 1) int64 delimit the groups.  vmap, vstem, syn_off, syn_ids
+    as ops.meteor takes them.  Synchronises the stream once (offsets and indices are checked on the host); not for
+    captured graphs."""
+    _need_cuda(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, hyp_idx, ref_idx, hyp_off, ref_off, cell_off, S)
+    G = _soda_offsets("meteor_matrix", hyp_off, ref_off, cell_off)
+    V = vmap.numel()
+    if hyp.dtype != torch.int64 or vmap.dtype != torch.int32 or ref.dtype != torch.int32 or ref_len.dtype != torch.int32 or \
+            hyp_idx.dtype != torch.int32 or ref_idx.dtype != torch.int32:
+        raise ValueError("meteor_matrix: hyp int64, vmap / ref / ref_len / hyp_idx / ref_idx int32 expected")
+    if hyp.dim() != 2 or ref.dim() != 2 or hyp.stride(1) != 1 or ref.stride(1) != 1 or ref_len.numel() != ref.shape[0] or \
+            not (vmap.is_contiguous() and ref_len.is_contiguous() and hyp_idx.is_contiguous() and ref_idx.is_contiguous()):
+        raise ValueError("meteor_matrix: hyp (Nh, L) and ref (Nr, R) with contiguous rows, ref_len (Nr), contiguous vmap and "
+                         "indices expected")
+    if (vstem is None) != (ref_stem is None):
+        raise ValueError("meteor_matrix: vstem and ref_stem go together")
+    if vstem is not None:
+        if vstem.dtype != torch.int32 or vstem.numel() != V or not vstem.is_contiguous():
+            raise ValueError("meteor_matrix: vstem (V) int32 expected")
+        if ref_stem.dtype != torch.int32 or ref_stem.shape != ref.shape or ref_stem.stride() != ref.stride():
+            raise ValueError("meteor_matrix: ref_stem int32, shaped and strided like ref, expected")
+    n_syn = 0
+    if syn_off is not None and syn_ids is not None:
+        n_syn = syn_ids.numel()
+        if syn_off.dtype != torch.int32 or syn_ids.dtype != torch.int32 or syn_off.numel() != V + 1 or n_syn < 1 or \
+                not syn_off.is_contiguous() or not syn_ids.is_contiguous():
+            raise ValueError("meteor_matrix: syn_off (V + 1) int32 and syn_ids (>= 1) int32 expected")
+    if S.dtype != torch.float64 or S.dim() != 1 or not S.is_contiguous():
+        raise ValueError("meteor_matrix: S (cells) fp64, contiguous, expected")
+    _lib.check(_lib.load().bmhrl_meteor_matrix(
+        hyp.data_ptr(), hyp.stride(0), hyp.shape[0], hyp.shape[1], vmap.data_ptr(), _p(vstem), V, _p(syn_off), _p(syn_ids),
+        n_syn, ref.data_ptr(), _p(ref_stem), ref.stride(0), ref_len.data_ptr(), ref.shape[0], ref.shape[1],
+        hyp_idx.data_ptr(), hyp_idx.numel(), ref_idx.data_ptr(), ref_idx.numel(), hyp_off.data_ptr(), ref_off.data_ptr(),
+        cell_off.data_ptr(), G, float(alpha), float(beta), float(gamma), S.data_ptr(), S.numel(), stream()),
+        "bmhrl_meteor_matrix")
+
+
+def soda_dp(pred_seg, ref_seg, hyp_off, ref_off, cell_off, S, tious):
+    """(G, T, 4) fp64 max_score, precision, recall, F of the time-ordered one-to-one assignment that maximises the sum of
+    tIoU x S per group and threshold; see bmhrl_soda_dp in include/bmhrl_hip.h.  pred_seg (sum P, 2) / ref_seg (sum R, 2)
+    fp64 start, end in matching order; the offsets and S as ops.meteor_matrix; tious (T) fp64 on the device.  Synchronises
+    the stream once; not for captured graphs."""
+    _need_cuda(pred_seg, ref_seg, hyp_off, ref_off, cell_off, S, tious)
+    G = _soda_offsets("soda_dp", hyp_off, ref_off, cell_off)
+    for t in (pred_seg, ref_seg):
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 2 or not t.is_contiguous():
+            raise ValueError("soda_dp: pred_seg / ref_seg (n, 2) fp64, contiguous, expected")
+    if S.dtype != torch.float64 or S.dim() != 1 or not S.is_contiguous() or tious.dtype != torch.float64 or \
+            tious.dim() != 1 or not tious.is_contiguous():
+        raise ValueError("soda_dp: S (cells) and tious (T) fp64, contiguous, expected")
+    T = tious.numel()
+    out = torch.empty(max(G, 0), T, 4, dtype=torch.float64, device=S.device)
+    _lib.check(_lib.load().bmhrl_soda_dp(pred_seg.data_ptr(), pred_seg.shape[0], ref_seg.data_ptr(), ref_seg.shape[0],
+                                         hyp_off.data_ptr(), ref_off.data_ptr(), cell_off.data_ptr(), G, S.data_ptr(), S.numel(),
+                                         tious.data_ptr(), T, out.data_ptr(), stream()), "bmhrl_soda_dp")
+    return out
+
+
 # ---- sampled caption decoding (csrc/sample.hip)
 SAMPLE_MAX_V = 16384                         # BMHRL_SAMPLE_MAX_V of include/bmhrl_hip.h
 

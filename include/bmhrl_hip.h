@@ -737,6 +737,48 @@ int bmhrl_caption_eval(const int32_t* hyp, int64_t ldh, const int32_t* hyp_len, 
                        bmhrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * SODA_c dense-captioning evaluation (bmhrl_amd/evaluate.py soda_scores; the rules are in DESIGN.md section 25).  A group
+ * is one (video, ground-truth file): P_g predictions in time order and R_g references in story order.  Both calls read
+ *  hyp_off / ref_off (G + 1) int32 and cell_off (G + 1) int64, device: group g owns the entries [hyp_off[g], hyp_off[g+1])
+ *  of the prediction-side arrays (n_pred entries in all), [ref_off[g], ref_off[g+1]) of the reference-side arrays (n_ref)
+ *  and the cells [cell_off[g], cell_off[g+1]) of S (n_cells), cell (i, j) at cell_off[g] + i * R_g + j.  Every offset
+ *  array starts at 0, never descends and ends at n_pred / n_ref / n_cells, and cell_off[g+1] - cell_off[g] = P_g * R_g;
+ *  a group with P_g = 0 or R_g = 0 owns no cell.  The offsets (and the indices below) are copied back and checked before
+ *  the launch, so each call synchronises the stream once and cannot be captured in a graph; nothing else is read back, and
+ *  S stays on the device between the two calls.  No atomics; equal inputs give equal bits.
+ *
+ * bmhrl_meteor_matrix: S[cell (i, j) of g] = the METEOR score of the whole hypothesis hyp_idx[hyp_off[g] + i] against the
+ *  reference ref_idx[ref_off[g] + j], fp64, with the bits of bmhrl_meteor's scores column L - 1 for that pair.
+ *  hyp (Nh, L) int64 vocab ids of the distinct hypotheses, row stride ldh (-1 and ids outside [0, V) yield no word; a
+ *  hypothesis without a word scores 0); vmap / vstem / V / syn_off / syn_ids / n_syn / alpha / beta / gamma as in
+ *  bmhrl_meteor; ref / ref_stem (Nr, R) int32 with one row stride ldr and ref_len (Nr) (device, clamped to [0, R]): the
+ *  distinct references; hyp_idx (n_pred) / ref_idx (n_ref) int32, device, inside [0, Nh) / [0, Nr).  One alignment per
+ *  cell; only the n_cells cells are written.  L <= BMHRL_REWARDS_MAX_L, R <= BMHRL_REWARDS_MAX_R, any P_g and R_g.
+ * bmhrl_soda_dp: out (G, T, 4) fp64 = max_score, precision, recall, F of every group at every threshold tious[t] (T,
+ *  fp64, device).  pred_seg (n_pred, 2) / ref_seg (n_ref, 2) fp64 start, end, in matching order.  With
+ *  iou = evaluate.tiou(prediction i, reference j) (intersection over the capped union plus 1e-8, in that function's order
+ *  of operations) and c[i][j] = (iou < tious[t] ? 0 : iou) * S[i][j]:
+ *  D[i][j] = max(D[i-1][j], D[i][j-1], D[i-1][j-1] + c[i][j]) with zero borders; max_score = D[P_g][R_g], precision =
+ *  max_score / P_g, recall = max_score / R_g, F = ((2 precision) recall) / (precision + recall), 0 when the sum is 0.  fp64
+ *  without contraction: the bits of the plain double loop.  A group with P_g = 0 or R_g = 0 writes four zeros.
+ *  R_g <= BMHRL_SODA_MAX_REFS, any P_g, 1 <= T <= BMHRL_SODA_MAX_T.
+ * Refused with -22 before any launch: a null required pointer, G <= 0, shapes past the limits or the row strides (Nh, Nr,
+ *  L, R, V < 1; ldh < L; ldr < R), vstem without ref_stem, exactly one of syn_off / syn_ids, negative counts, offsets that
+ *  break the rules above, indices outside their range.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_SODA_MAX_REFS 256
+#define BMHRL_SODA_MAX_T 16
+int bmhrl_meteor_matrix(const int64_t* hyp, int64_t ldh, int32_t Nh, int32_t L, const int32_t* vmap, const int32_t* vstem,
+                        int32_t V, const int32_t* syn_off, const int32_t* syn_ids, int32_t n_syn, const int32_t* ref,
+                        const int32_t* ref_stem, int64_t ldr, const int32_t* ref_len, int32_t Nr, int32_t R,
+                        const int32_t* hyp_idx, int32_t n_pred, const int32_t* ref_idx, int32_t n_ref, const int32_t* hyp_off,
+                        const int32_t* ref_off, const int64_t* cell_off, int32_t G, double alpha, double beta, double gamma,
+                        double* S, int64_t n_cells, bmhrl_stream_t stream);
+int bmhrl_soda_dp(const double* pred_seg, int32_t n_pred, const double* ref_seg, int32_t n_ref, const int32_t* hyp_off,
+                  const int32_t* ref_off, const int64_t* cell_off, int32_t G, const double* S, int64_t n_cells,
+                  const double* tious, int32_t T, double* out, bmhrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sampled caption decoding (bmhrl_amd/decode.py SampleDecoder; the rules are at the top of its sampling section).  One step
  * for every row r of logp (rows, ld) fp32 log-probs, t read from the device word t[0]:
  *  finished[r] != 0: tok[r] = pad_idx, out[r][t + 1] = pad_idx, step_logp / step_logq [r][t] = 0, sum_logp unchanged;
