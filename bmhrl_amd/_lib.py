@@ -152,6 +152,10 @@ PROTOTYPES = {
     "bmhrl_lsa_match": [ptr, i64, i64, i64, ptr, i32, i32, i32, ptr, ptr],
     "bmhrl_word_loss": [ptr, ptr, ptr, ptr, ptr, ptr, ptr, f32, i32, i32, i32, i32, ptr, ptr, ptr, ptr],
     "bmhrl_word_loss_bwd": [ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr, ptr, i64, i32, i32, i32, ptr],
+    "bmhrl_proposal_assign": [ptr, i32, ptr, i32, f32, i32, i32, ptr, ptr, ptr, ptr, ptr],
+    "bmhrl_proposal_head": [ptr, ptr, f32, i32, i32, i32, ptr, i64, i64, ptr, ptr, ptr, ptr, f32, f32, ptr, ptr, ptr, ptr, ptr,
+                            ptr],
+    "bmhrl_proposal_select": [ptr, i32, i64, ptr, i32, f32, ptr, ptr, ptr, i64, ptr],
 }
 
 _lib = None

@@ -2313,3 +2313,28 @@ class SegmentCriticFn(torch.autograd.Function):
                 if li == 0:
                     demb = dx.view(B, L, d)
         return (demb, *grads) + ((None, None, None) if ctx.with_loss else ())
+
+
+class ProposalLossFn(torch.autograd.Function):
+    """One anchor head of the proposal generator (csrc/proposal.hip): apply(x (B, S, 3A), anchors (A),
+    cell_sec, pred, row_off, owner, tx, tw, counts, obj_coeff, noobj_coeff, sums) writes the head's rows of pred (B, N_total,
+    3) = [centre s, length s, confidence] and sums (5) = [loss_x, loss_w, loss_obj, loss_noobj, total] in ONE launch and
+    returns the total.  loss_obj / loss_noobj are softplus(-o) / softplus(o): the BCELoss of sigmoid(o) against 1 / 0
+    everywhere torch does not clamp its log at -100 (|o| beyond 100).  The same launch stores d total / d x; backward is that
+    tensor times the incoming scalar.  pred and sums are written in place and carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, anchors, cell_sec, pred, row_off, owner, tx, tw, counts, obj_coeff, noobj_coeff, sums):
+        x32 = x.detach()
+        x32 = (x32 if x32.dtype == torch.float32 else x32.float()).contiguous()
+        dx = torch.empty_like(x32) if ctx.needs_input_grad[0] else None
+        ops.proposal_head(x32, anchors, cell_sec, pred, row_off, (owner, tx, tw, counts), obj_coeff, noobj_coeff, sums=sums, dx=dx)
+        ctx.save_for_backward(dx)
+        ctx.in_dtype = x.dtype
+        return sums[4].clone()
+
+    @staticmethod
+    def backward(ctx, dtotal):
+        dx, = ctx.saved_tensors
+        g = dx * dtotal
+        return (g if ctx.in_dtype == torch.float32 else g.to(ctx.in_dtype),) + (None,) * 11

@@ -1233,3 +1233,104 @@ def word_loss_bwd(logits, lse, tgt_class, row_w, loss_scale, g=None, out=None):
                                                tgt_class.data_ptr(), row_w.data_ptr(), loss_scale.data_ptr(), _p(g), out.data_ptr(), ldd, B, Q, Cn, stream()),
                "bmhrl_word_loss_bwd")
     return out
+
+
+# ---- temporal proposal generation: target assignment, head decode + loss, top-k + NMS (csrc/proposal.hip)
+PROPOSAL_MAX_K = 128                          # BMHRL_PROPOSAL_MAX_K of include/bmhrl_hip.h
+PROPOSAL_MAX_N = 1 << 24                      # BMHRL_PROPOSAL_MAX_N
+_PROPOSAL_CHUNK = 4096                        # keys sorted per block (csrc/proposal.hip kChunk)
+
+
+def _f32c(t, shape, what):
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous fp32 tensor of shape {tuple(shape)}")
+
+
+def proposal_assign(targets, anchors, cell_sec, B, S):
+    """target assignment of one modality (see bmhrl_proposal_assign): targets (N, 4) fp32 rows [video index, centre s,
+    length s, meta index], anchors (A) fp32 seconds.  Returns owner (B, A, S) int32 (the target row that owns the cell, -1
+    for none), tx (N), tw (N) fp32 and counts (2) int32 = [owned cells, the others], all on the device."""
+    _need_cuda(targets, anchors)
+    if targets.dim() != 2 or targets.shape[1] != 4 or anchors.dim() != 1:
+        raise ValueError("proposal_assign: targets (N, 4) and anchors (A) expected")
+    N, A = targets.shape[0], anchors.shape[0]
+    _f32c(targets, (N, 4), "proposal_assign (targets)")
+    _f32c(anchors, (A,), "proposal_assign (anchors)")
+    dev = anchors.device
+    owner = torch.empty(B, A, S, dtype=torch.int32, device=dev)
+    tx = torch.empty(N, device=dev)
+    tw = torch.empty(N, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().bmhrl_proposal_assign(targets.data_ptr() if N else None, N, anchors.data_ptr(), A, float(cell_sec),
+                                                 int(B), int(S), owner.data_ptr(), tx.data_ptr() if N else None,
+                                                 tw.data_ptr() if N else None, counts.data_ptr(), stream()),
+               "bmhrl_proposal_assign")
+    return owner, tx, tw, counts
+
+
+def proposal_head(x, anchors, cell_sec, pred, row_off, assigned=None, obj_coeff=1.0, noobj_coeff=100.0, sums=None, dx=None,
+                  dscale=None):
+    """decode, loss and gradient of one head (see bmhrl_proposal_head): x (B, S, 3A) fp32, pred (B, N_total, 3) fp32 whose
+    rows row_off .. row_off + A*S - 1 are written.  assigned = proposal_assign's (owner, tx, tw, counts) selects training:
+    sums (5) fp32 = [loss_x, loss_w, loss_obj, loss_noobj, total] is written (allocated when None) and dx (B, S, 3A), when
+    given, gets dscale * d total / d x.  assigned=None is inference: predictions only.  Returns sums (None in inference)."""
+    _need_cuda(x, anchors, pred, sums, dx, dscale)
+    if x.dim() != 3 or anchors.dim() != 1 or x.shape[2] != 3 * anchors.shape[0] or pred.dim() != 3:
+        raise ValueError("proposal_head: x (B, S, 3A), anchors (A) and pred (B, N_total, 3) expected")
+    B, S, A = x.shape[0], x.shape[1], anchors.shape[0]
+    _f32c(x, (B, S, 3 * A), "proposal_head (x)")
+    _f32c(anchors, (A,), "proposal_head (anchors)")
+    _f32c(pred, (B, pred.shape[1], 3), "proposal_head (pred)")
+    dev = x.device
+    owner = tx = tw = counts = partials = counter = None
+    if assigned is not None:
+        owner, tx, tw, counts = assigned
+        if owner.dtype != torch.int32 or tuple(owner.shape) != (B, A, S) or not owner.is_contiguous() or \
+                counts.dtype != torch.int32 or counts.numel() != 2:
+            raise ValueError("proposal_head: assigned must be proposal_assign's result for this head's (B, A, S)")
+        if sums is None:
+            sums = torch.empty(5, device=dev)
+        _f32c(sums, (5,), "proposal_head (sums)")
+        if dx is not None:
+            _f32c(dx, (B, S, 3 * A), "proposal_head (dx)")
+        if dscale is not None and (dscale.dtype != torch.float32 or dscale.numel() != 1):
+            raise ValueError("proposal_head: dscale is a (1,) fp32 device scalar")
+        partials = torch.empty(4 * 1024, device=dev)                    # 4 * BMHRL_PROPOSAL_HEAD_BLOCKS
+        counter = torch.empty(4, dtype=torch.int32, device=dev)        # the ticket word (the call zeroes it on the stream)
+    elif dx is not None or sums is not None:
+        raise ValueError("proposal_head: sums and dx need assigned targets")
+    _lib.check(_lib.load().bmhrl_proposal_head(x.data_ptr(), anchors.data_ptr(), float(cell_sec), B, S, A, pred.data_ptr(),
+                                               pred.shape[1], int(row_off), _p(owner), _p(tx), _p(tw), _p(counts),
+                                               float(obj_coeff), float(noobj_coeff), _p(dscale), _p(dx), _p(sums), _p(partials),
+                                               _p(counter), stream()), "bmhrl_proposal_head")
+    return sums
+
+
+def proposal_select_workspace(N, k):
+    """64-bit words per video bmhrl_proposal_select needs"""
+    if N <= _PROPOSAL_CHUNK:
+        return 0
+    c1 = -(-N // _PROPOSAL_CHUNK) * k
+    return c1 + -(-c1 // _PROPOSAL_CHUNK) * k
+
+
+def proposal_select(predictions, durations, k, nms_tiou=None):
+    """top-k + corner coordinates + trimming + greedy NMS of a batch (see bmhrl_proposal_select): predictions (B, N, 3) fp32
+    rows [centre s, length s, confidence], durations (B) fp32, nms_tiou None = no suppression.  Returns props (B, k, 3) =
+    [start, end, confidence], survivors first in confidence order and zeros behind them, and count (B) int32."""
+    _need_cuda(predictions, durations)
+    if predictions.dim() != 3 or predictions.shape[2] != 3:
+        raise ValueError("proposal_select: predictions (B, N, 3) expected")
+    B, N = predictions.shape[0], predictions.shape[1]
+    _f32c(predictions, (B, N, 3), "proposal_select (predictions)")
+    _f32c(durations, (B,), "proposal_select (durations)")
+    k = int(k)
+    dev = predictions.device
+    props = torch.empty(B, max(k, 0), 3, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    words = B * proposal_select_workspace(N, k) if 1 <= k <= PROPOSAL_MAX_K else 0
+    ws = torch.empty(words, dtype=torch.int64, device=dev) if words else None
+    _lib.check(_lib.load().bmhrl_proposal_select(predictions.data_ptr(), B, N, durations.data_ptr(), k,
+                                                 -1.0 if nms_tiou is None else float(nms_tiou), props.data_ptr(),
+                                                 count.data_ptr(), _p(ws), words, stream()), "bmhrl_proposal_select")
+    return props, count

@@ -1,0 +1,204 @@
+"""Post-processing of the proposal generator's predictions, the counterpart of the reference's utilities/proposal_utils.py:
+tIoU, top-k, corner coordinates, trimming, greedy NMS, the ActivityNet submission dictionary and anchor lengths.
+
+The tensor functions reproduce the reference's results (tests/golden/proposals.json / .npz record them) for callers that use them
+piecemeal; they are plain torch and run wherever their input lives.  `AnetPredictions.add_new_predictions` does the whole
+chain for a batch: for device input in ONE call of ops.proposal_select (csrc/proposal.hip: a fixed number of launches and no
+host read before the single `.tolist()`), for host input through the piecewise functions.  Where the reference's `argsort`
+leaves the order of equal confidences open, both routes here put the smaller row first.
+
+`anchors_from_segments` stands where the reference's `calc_anchors_using_kmeans` stands.  That one runs scikit-learn's KMeans
+with a random initialisation (random_state=13); scikit-learn's generator is not reproduced here.  This is a deterministic
+1-D k-means (Lloyd's iterations from quantile initial centres), so its anchors are close to, not equal to, the reference's.
+"""
+from __future__ import annotations
+
+import contextlib
+import io
+import json
+import os
+from time import time
+
+import numpy as np
+import torch
+
+
+def tiou_vectorized(segments1, segments2, without_center_coords=False, center_length=True):
+    """(M, N) temporal IoU of every pair.  Rows are (centre, length) when center_length, else (start, end); with
+    without_center_coords the inputs are (M, 1) / (N, 1) lengths laid on a common centre."""
+    if without_center_coords:
+        segments1 = torch.cat([torch.zeros_like(segments1), segments1], dim=1)
+        segments2 = torch.cat([torch.zeros_like(segments2), segments2], dim=1)
+    M, N = segments1.shape[0], segments2.shape[0]
+    if center_length:
+        s1, e1 = segments1[:, 0] - segments1[:, 1] / 2, segments1[:, 0] + segments1[:, 1] / 2
+        s2, e2 = segments2[:, 0] - segments2[:, 1] / 2, segments2[:, 0] + segments2[:, 1] / 2
+    else:
+        s1, e1 = segments1[:, 0], segments1[:, 1]
+        s2, e2 = segments2[:, 0], segments2[:, 1]
+    s1, e1 = s1.view(M, 1), e1.view(M, 1)
+    s2, e2 = s2.view(1, N), e2.view(1, N)
+    inter = torch.clamp(torch.min(e1, e2) - torch.max(s1, s2), min=0.0)
+    union = (e1 - s1) + (e2 - s2) - inter
+    union = torch.min(torch.max(e1, e2) - torch.min(s1, s2), union)      # never more than the hull
+    return inter / (union + 1e-8)
+
+
+def calculate_f1(recall, precision):
+    return 2 * recall * precision / (recall + precision + 1e-16)
+
+
+def add_dict_to_another_dict(one_dict, another_dict):
+    return {k: another_dict.get(k, 0) + v for k, v in one_dict.items()}
+
+
+def get_lr(optimizer):
+    for group in optimizer.param_groups:
+        return group["lr"]
+
+
+def get_corner_coords(predictions):
+    """(B, N, >=2) rows (centre, length, ...) -> (start, end, ...), in place as the reference does"""
+    starts = predictions[:, :, 0] - predictions[:, :, 1] / 2
+    ends = predictions[:, :, 0] + predictions[:, :, 1] / 2
+    predictions[:, :, 0] = starts
+    predictions[:, :, 1] = ends
+    return predictions
+
+
+def select_topk_predictions(model_output, k):
+    """(B, N, F) -> the k rows of highest confidence (column 2) per video, in that order; equal confidences keep their row
+    order (a stable sort: the reference's argsort does not say)"""
+    B, N, F = model_output.shape
+    order = model_output[:, :, 2].argsort(descending=True, stable=True)
+    return model_output.gather(1, order.view(B, N, 1).expand(B, N, F))[:, :k, :]
+
+
+def trim_proposals(model_output, duration_in_secs):
+    """clip starts to [0, duration] and ends to (-inf, duration], in place"""
+    dur = torch.as_tensor(duration_in_secs, dtype=model_output.dtype, device=model_output.device).view(-1, 1)
+    zero = torch.zeros(1, dtype=model_output.dtype, device=model_output.device)
+    model_output[:, :, 0] = torch.min(torch.max(model_output[:, :, 0], zero), dur)
+    model_output[:, :, 1] = torch.min(model_output[:, :, 1], dur)
+    return model_output
+
+
+def non_max_suppresion(video_preds, tIoU_threshold):
+    """greedy NMS of one video's (n, F) rows (start, end, ...) sorted by confidence: a kept row removes every later one whose
+    tIoU with it is not below the threshold.  (The name is the reference's.)"""
+    kept = []
+    while len(video_preds) > 0:
+        kept.append(video_preds[0:1, :])
+        if len(video_preds) == 1:
+            break
+        tious = tiou_vectorized(video_preds[0:1, :], video_preds[1:, :], center_length=False).reshape(-1)
+        video_preds = video_preds[1:, :][tious < tIoU_threshold]
+    return torch.cat(kept) if kept else video_preds
+
+
+def postprocess_preds(model_output, cfg, batch):
+    """top-cfg.max_prop_per_vid rows, corner coordinates in seconds, trimmed to the videos' durations: (B, k, F)"""
+    model_output = select_topk_predictions(model_output, k=cfg.max_prop_per_vid)
+    model_output = get_corner_coords(model_output)
+    return trim_proposals(model_output, batch["duration_in_secs"])
+
+
+class AnetPredictions:
+    """collects a validation pass's proposals in the ActivityNet-captions submission layout (the reference's class of the
+    same name: same dictionary, same counters, same file name)"""
+
+    def __init__(self, cfg, phase, epoch):
+        self.predictions = {"version": "VERSION 1.0", "external_data": {"used": True, "details": ""}, "results": {}}
+        self.phase = phase
+        self.epoch = epoch
+        self.cfg = cfg
+        self.segments_used = 0
+        self.segments_total = 0
+        self.num_vid_w_no_props = 0
+
+    def _device_rows(self, model_output, batch):
+        """per video the surviving (start, end, conf) rows as Python lists, after ONE device-to-host copy"""
+        from . import ops
+        B = model_output.shape[0]
+        dur = torch.as_tensor(batch["duration_in_secs"], dtype=torch.float32).to(model_output.device, non_blocking=True)
+        k = int(self.cfg.max_prop_per_vid)
+        props, count = ops.proposal_select(model_output.detach().float().contiguous(), dur, k, self.cfg.nms_tiou_thresh)
+        packed = torch.cat([props.view(B, -1), count.view(B, 1).to(props.dtype)], dim=1).tolist()
+        return [[row[3 * j:3 * j + 3] for j in range(int(row[-1]))] for row in packed], min(k, model_output.shape[1])
+
+    def _host_rows(self, model_output, batch):
+        model_output = postprocess_preds(model_output, self.cfg, batch)
+        rows = []
+        for video_preds in model_output:
+            if self.cfg.nms_tiou_thresh is not None:
+                video_preds = non_max_suppresion(video_preds, self.cfg.nms_tiou_thresh)
+            rows.append(video_preds.tolist())
+        return rows, model_output.shape[1]
+
+    def add_new_predictions(self, model_output, batch):
+        """model_output (B, N, 3) rows (centre s, length s, confidence).  Returns the proposals written per video."""
+        from . import ops
+        B = model_output.shape[0]
+        on_device = model_output.is_cuda and 1 <= int(self.cfg.max_prop_per_vid) <= ops.PROPOSAL_MAX_K and \
+            1 <= model_output.shape[1] <= ops.PROPOSAL_MAX_N and model_output.shape[2] == 3
+        rows, k = self._device_rows(model_output, batch) if on_device else self._host_rows(model_output, batch)
+        written = 0
+        shortest = 0.2      # seconds
+        for b, video_rows in enumerate(rows):
+            vid_preds = []
+            for pred_start, pred_end, pred_conf in video_rows:
+                start, end = round(pred_start, 5), round(pred_end, 5)
+                if end - start > shortest:
+                    # (the score is a one-element tuple in the reference: a trailing comma there; json writes it as a list)
+                    vid_preds.append({"sentence": "", "proposal_score": (round(pred_conf, 5),), "timestamp": [start, end]})
+                    written += 1
+            if vid_preds:
+                self.predictions["results"][batch["video_ids"][b]] = vid_preds
+            else:
+                self.num_vid_w_no_props += 1
+        self.segments_total += B * k
+        self.segments_used += written
+        return written / B
+
+    def write_anet_predictions_to_json(self):
+        if self.phase != "val_1":       # val_1 and val_2 share their proposals; the reference writes val_1 only
+            raise NotImplementedError
+        folder = os.path.join(self.cfg.log_path, "submissions")
+        name = f"prop_results_{self.phase}_e{self.epoch}_maxprop{self.cfg.max_prop_per_vid}.json"
+        self.submission_path = os.path.join(folder, name)
+        os.makedirs(folder, exist_ok=True)
+        if os.path.exists(self.submission_path):
+            self.submission_path = self.submission_path.replace(".json", f"_{time()}.json")
+        with open(self.submission_path, "w") as f:
+            json.dump(self.predictions, f)
+
+    def evaluate_predictions(self):
+        from .epoch_loops.validation_loops import calculate_metrics
+        print(f"{self.cfg.max_prop_per_vid * self.segments_used / max(self.segments_total, 1):.2f} props/vid")
+        if self.num_vid_w_no_props > 0:
+            print(f"Number of videos with no proposals: {self.num_vid_w_no_props}")
+        with contextlib.redirect_stdout(io.StringIO()):
+            return calculate_metrics(self.cfg.reference_paths, self.submission_path, self.cfg.tIoUs, self.cfg.max_prop_per_vid,
+                                     verbose=True, only_proposals=True, evaluator=getattr(self.cfg, "caption_evaluator", None))
+
+
+def anchors_from_segments(lengths, k, iters=100):
+    """k anchor lengths (sorted list of floats) from ground-truth segment lengths: 1-D k-means, deterministic -- initial
+    centres at the quantiles (i + 0.5) / k, Lloyd's iterations until nothing moves or `iters` are done, a cluster that
+    loses all its points keeps its centre.  See the module docstring for how this relates to the reference's KMeans."""
+    x = np.sort(np.asarray(lengths, dtype=np.float64).reshape(-1))
+    x = x[x > 0]
+    if k < 1 or x.size < k:
+        raise ValueError(f"anchors_from_segments: need at least k = {k} positive lengths, got {x.size}")
+    centres = np.quantile(x, (np.arange(k) + 0.5) / k)
+    for _ in range(iters):
+        edges = (centres[1:] + centres[:-1]) / 2            # sorted centres: clusters are intervals
+        label = np.searchsorted(edges, x, side="left")
+        sums = np.bincount(label, weights=x, minlength=k)
+        cnts = np.bincount(label, minlength=k)
+        new = np.where(cnts > 0, sums / np.maximum(cnts, 1), centres)
+        new.sort()
+        if np.array_equal(new, centres):
+            break
+        centres = new
+    return [float(c) for c in centres]

@@ -879,6 +879,49 @@ int bmhrl_word_loss_bwd(const float* logits, int64_t ld, const float* lse, const
                         const float* row_w, const float* loss_scale, const float* g, float* dlogits, int64_t ldd, int32_t B,
                         int32_t Q, int32_t C, bmhrl_stream_t stream);
 
+/* ---- temporal proposal generation (csrc/proposal.hip) -------------------------------------------
+ * Anchor heads in the YOLO style: head h of a modality sees S feature positions of cell_sec seconds each and predicts, for
+ * each of the modality's A anchor lengths (seconds), a centre offset, a log length factor and an objectness logit.  All
+ * launches are ordinary launches on the caller's stream, none reads back to the host, and equal inputs give equal bits.
+ * Bad shapes and null required pointers are refused with -22 and launch nothing.
+ *
+ * bmhrl_proposal_assign: targets (n_targets, 4) fp32 rows [video index in batch, centre s, length s, unused]; anchors (A).
+ *  For row r: g = centre / cell_sec, w = length / cell_sec, cell = floor(g); the best anchor is the argmax over a of the
+ *  tIoU of the lengths anchors[a] / cell_sec and w laid on a common centre (fp32, the reference's tiou_vectorized arithmetic
+ *  with without_center_coords), ties to the smaller a.  Writes tx[r] = g - floor(g), tw[r] = log(w / (anchors[best] /
+ *  cell_sec) + 1e-16) for every row, and owner (B, A, S) int32: the LARGEST r whose (video, best anchor, cell) it is, -1
+ *  where none is; rows whose video index or cell is outside [0, B) x [0, S) own nothing.  counts[0] = number of owned
+ *  cells, counts[1] = B * A * S - counts[0].  B * A * S <= INT32_MAX.
+ * bmhrl_proposal_head: x (B, S, 3 A) fp32 contiguous, channel 3 a + {0, 1, 2} = (c, l, o) of anchor a.  Writes the rows
+ *  row_off + a * S + s of pred (B, n_total, 3): [(sigmoid(c) + s) * cell_sec, anchors[a] * exp(l), sigmoid(o)].
+ *  With owner (training): sums[0..4] = loss_x, loss_w, loss_obj, loss_noobj, total, where
+ *   loss_x = mean over owned cells of (sigmoid(c) - tx[r])^2      loss_w = mean over owned cells of (l - tw[r])^2
+ *   loss_obj = mean over owned cells of softplus(-o)               loss_noobj = mean over the other cells of softplus(o)
+ *   total = loss_x + loss_w + obj_coeff * loss_obj + noobj_coeff * loss_noobj,
+ *  a mean over no cell being 0 (softplus(-o) and softplus(o) are torch's BCELoss of sigmoid(o) against 1 and 0 wherever
+ *  that does not clamp its logarithm at -100); and, when dx is given, dx (B, S, 3 A) = dscale[0] * d total / d x (dscale null = 1), every
+ *  element stored.  partials: 4 * BMHRL_PROPOSAL_HEAD_BLOCKS fp32 scratch; counter: 16 bytes of scratch, 16-byte aligned,
+ *  zeroed by the call itself (on the stream).  The block sums are fp32 in a fixed order, their sum over the blocks fp64 in index
+ *  order.  Without owner (inference): predictions only; dx must be null, sums / partials / counter are not touched.
+ * bmhrl_proposal_select: pred (B, N, 3) fp32 rows [centre s, length s, confidence], durations (B) fp32.  Per video: the
+ *  min(k, N) rows of highest confidence, ties to the smaller row; start = centre - length / 2, end = centre + length / 2;
+ *  start = min(max(start, 0), duration), end = min(end, duration); then, when nms_tiou >= 0, greedy suppression in that
+ *  order: a kept segment removes every later one whose tIoU with it is not < nms_tiou (tIoU = intersection / (min(hull,
+ *  sum of lengths - intersection) + 1e-8), fp32, IEEE division).  props (B, k, 3) = [start, end, confidence] of the
+ *  survivors in order, zeros behind them; count (B) int32.  1 <= k <= BMHRL_PROPOSAL_MAX_K, 1 <= N <= BMHRL_PROPOSAL_MAX_N.
+ *  workspace: 64-bit words, needed when N > 4096: with c(m) = ceil(m / 4096) * k, B * (c(N) + c(c(N))) words are enough. */
+#define BMHRL_PROPOSAL_MAX_K 128
+#define BMHRL_PROPOSAL_HEAD_BLOCKS 1024
+#define BMHRL_PROPOSAL_MAX_N (1 << 24)
+int bmhrl_proposal_assign(const float* targets, int32_t n_targets, const float* anchors, int32_t A, float cell_sec, int32_t B,
+                          int32_t S, int32_t* owner, float* tx, float* tw, int32_t* counts, bmhrl_stream_t stream);
+int bmhrl_proposal_head(const float* x, const float* anchors, float cell_sec, int32_t B, int32_t S, int32_t A, float* pred,
+                        int64_t n_total, int64_t row_off, const int32_t* owner, const float* tx, const float* tw,
+                        const int32_t* counts, float obj_coeff, float noobj_coeff, const float* dscale, float* dx, float* sums,
+                        float* partials, uint32_t* counter, bmhrl_stream_t stream);
+int bmhrl_proposal_select(const float* pred, int32_t B, int64_t N, const float* durations, int32_t k, float nms_tiou,
+                          float* props, int32_t* count, uint64_t* workspace, int64_t workspace_elems, bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
