@@ -6,7 +6,10 @@ decoder is bmhrl_amd.decode (per-clip memory K|V, incremental caption K|V cache,
 ids -> words, cut at </s>, capitalise, the ActivityNet-captions result dictionary and its JSON file -- keeps the reference's
 format so that its evaluator reads the file unchanged.  The file is scored by the reference's evaluator
 (evaluation/evaluate.py: Java METEOR, PTB tokenizer) when that is on sys.path -- otherwise the loop returns after writing
-the predictions -- or, with evaluator="device" / cfg.caption_evaluator = "device", by bmhrl_amd.evaluate on the device."""
+the predictions -- or, with evaluator="device" / cfg.caption_evaluator = "device", by bmhrl_amd.evaluate on the device.
+
+validation_learned_props_loop captions predicted proposals (the reference's `learned_props` phase) from the videos' full-length
+feature stacks through bmhrl_amd.predict, and writes and scores its file the same way."""
 import contextlib
 import io
 import json
@@ -85,6 +88,24 @@ def calculate_metrics(reference_paths, submission_path, tIoUs, max_prop_per_vid,
     return metrics
 
 
+def _write_and_score(cfg, predictions, phase, epoch, reference_paths, tIoUs, evaluator):
+    """writes captioning_results_<phase>_e<epoch>.json under cfg.log_path and scores it: the metrics dictionary, or
+    `predictions` itself (with its "submission_path") when the evaluator is not importable"""
+    os.makedirs(cfg.log_path, exist_ok=True)
+    path = os.path.join(cfg.log_path, f"captioning_results_{phase}_e{epoch}.json")
+    if os.path.exists(path):          # another loader / pretrained model in the same run: keep both files
+        path = path.replace(".json", f"_{time()}.json")
+    with open(path, "w") as f:
+        json.dump(predictions, f)
+    try:
+        with contextlib.redirect_stdout(io.StringIO()):
+            return calculate_metrics(reference_paths, path, tIoUs, cfg.max_prop_per_vid, evaluator=evaluator,
+                                     evaluator_options=getattr(cfg, "caption_evaluator_options", None))
+    except NotImplementedError:
+        predictions["submission_path"] = path
+        return predictions
+
+
 def validation_1by1_loop(cfg, model, loader, decoder, epoch, TBoard, evaluator=None):
     """Greedy-decode the whole loader, write captioning_results_<phase>_e<epoch>.json under cfg.log_path and score it.
     Returns the metrics dictionary; None when cfg.log_path is None (as the reference); the predictions dictionary when the
@@ -101,18 +122,8 @@ def validation_1by1_loop(cfg, model, loader, decoder, epoch, TBoard, evaluator=N
     predictions = predict_1by1(cfg, model, loader, decoder)
     if cfg.log_path is None:
         return None
-    os.makedirs(cfg.log_path, exist_ok=True)
-    path = os.path.join(cfg.log_path, f"captioning_results_{phase}_e{epoch}.json")
-    if os.path.exists(path):          # another loader / pretrained model in the same run: keep both files
-        path = path.replace(".json", f"_{time()}.json")
-    with open(path, "w") as f:
-        json.dump(predictions, f)
-    try:
-        with contextlib.redirect_stdout(io.StringIO()):
-            val_metrics = calculate_metrics(reference_paths, path, tIoUs, cfg.max_prop_per_vid, evaluator=evaluator,
-                                            evaluator_options=getattr(cfg, "caption_evaluator_options", None))
-    except NotImplementedError:
-        predictions["submission_path"] = path
+    val_metrics = _write_and_score(cfg, predictions, phase, epoch, reference_paths, tIoUs, evaluator)
+    if val_metrics is predictions:
         return predictions
     if TBoard is not None and phase != "learned_props":
         avg = val_metrics["Average across tIoUs"]
@@ -139,3 +150,48 @@ def validation_next_word_loop(cfg, model, loader, decoder, criterion, epoch, TBo
             n_tokens = (cap_y != pad_idx).sum()
             total += (criterion(pred, cap_y) / n_tokens).item()
     return total / len(loader)
+
+
+def _video_durations(reference_paths):
+    """video id -> duration in seconds from the ground-truth files (ActivityNet-captions layout: {id: {"duration", ...}})"""
+    durations = {}
+    for path in reference_paths:
+        with open(path) as f:
+            for video_id, entry in json.load(f).items():
+                durations.setdefault(video_id, float(entry["duration"]))
+    return durations
+
+
+def validation_learned_props_loop(cfg, model, proposals, decoder, epoch, TBoard, dataset, evaluator=None):
+    """Captions predicted proposals -- the reference's `learned_props` phase -- from the videos' full-length feature files:
+    `proposals` is a submission dictionary or the path of a prop_results_*.json.  Its segments are grouped by video in the
+    file's order; cfg.inference_batch_size videos at a time are loaded whole (predict.VideoFeatures: each file read once,
+    onto cfg.device) and their segments cropped there and captioned in chunks of cfg.inference_batch_size by
+    predict.caption_segments.  Durations come from the ground-truth files cfg.reference_paths.  Writes
+    captioning_results_learned_props_e<epoch>.json and scores it against cfg.reference_paths at cfg.tIoUs; returns as
+    validation_1by1_loop: the metrics, None when cfg.log_path is None, the predictions dictionary when the evaluator is not
+    importable.  dataset: vocabulary and special tokens (train_vocab.itos, start_idx, end_idx, pad_idx)."""
+    from ..predict import VideoFeatures, caption_segments
+    if evaluator is None:
+        evaluator = getattr(cfg, "caption_evaluator", None)
+    model.eval()
+    if isinstance(proposals, (str, os.PathLike)):
+        with open(proposals) as f:
+            proposals = json.load(f)
+    reference_paths, tIoUs = _phase_references(cfg, "learned_props")
+    durations = _video_durations(reference_paths)
+    videos = list(proposals["results"].items())
+    predictions = {"version": "VERSION 1.0", "external_data": {"used": True, "details": ""}, "results": {}}
+    step = int(cfg.inference_batch_size)
+    for i in range(0, len(videos), step):
+        group = videos[i:i + step]
+        ids = [video_id for video_id, _ in group]
+        features = VideoFeatures.from_npy(cfg, ids, [durations[v] for v in ids], cfg.pad_feats_up_to, dataset.pad_idx,
+                                          torch.device(cfg.device))
+        segments = [[tuple(seg["timestamp"]) for seg in segs] for _, segs in group]
+        for video_id, caps in zip(ids, caption_segments(cfg, model, features, segments, decoder, dataset)):
+            if caps:
+                predictions["results"].setdefault(video_id, []).extend(caps)
+    if cfg.log_path is None:
+        return None
+    return _write_and_score(cfg, predictions, "learned_props", epoch, reference_paths, tIoUs, evaluator)

@@ -15,9 +15,13 @@ Here:
 
 Same values as the reference's batch (tests/test_loader_cpu.py pins crop_bounds / pack against fixtures generated from the
 reference's own functions), same dict keys, same dtypes.  The upload needs a GPU; packing is plain host code.
+
+`crop_segments_host` restates ops.crop_segments (csrc/segment_crop.hip: the same clips cut out of full-length stacks that are
+already on the device, bmhrl_amd/predict.py) on CPU tensors, from crop_bounds and plain indexing.
 """
 from __future__ import annotations
 
+import math
 import os
 import threading
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -41,6 +45,52 @@ def crop_bounds(S: int, start: float, end: float, duration: float) -> Optional[T
             b += 1
     lo, hi, _ = slice(a, b).indices(S)                 # what feature[a:b] keeps
     return (lo, hi) if hi > lo else None
+
+
+def crop_rows(S: int, start: float, end: float, duration: float) -> Tuple[int, int, bool]:
+    """(lo, n, defined) of a segment of a stack of S rows: crop_bounds as (first row, row count), (0, 0) for an empty crop;
+    defined is False -- and the crop empty -- where crop_bounds has no answer: duration not > 0, or a quotient or product that
+    is not finite (int() would raise)."""
+    S, start, end, duration = int(S), float(start), float(end), float(duration)
+    if not duration > 0.0:
+        return 0, 0, False
+    qa, qb = start / duration, end / duration
+    if not all(math.isfinite(x) for x in (qa, qb, S * qa, S * qb)):
+        return 0, 0, False
+    r = crop_bounds(S, start, end, duration)
+    return (r[0], r[1] - r[0], True) if r else (0, 0, True)
+
+
+def crop_segments_host(src, src_len, durations, seg_video, seg_times, pad_value, T_out):
+    """ops.crop_segments restated on the host with crop_bounds and plain indexing, for CPU tensors or arrays: src (V, S_pad,
+    D), src_len (V), durations (V), seg_video (P), seg_times (P, 2).  Returns out (P, T_out, D) fp32, lengths (P) int32 (not
+    clipped to T_out), lo (P) int32 and status (2) int32 = [segments longer than T_out, segments without a defined crop].
+    A clip is laid out as FeaturePacker.pack lays it out: its rows, then pad_value; an empty crop is one zero row, then
+    pad_value."""
+    src = torch.as_tensor(src, dtype=torch.float32)
+    V, S_pad, D = src.shape
+    src_len, durations = np.asarray(src_len).reshape(-1), np.asarray(durations, dtype=np.float64).reshape(-1)
+    seg_video, seg_times = np.asarray(seg_video).reshape(-1), np.asarray(seg_times, dtype=np.float64).reshape(-1, 2)
+    P, T_out = seg_video.shape[0], int(T_out)
+    if min(V, S_pad, D, P, T_out) < 1:
+        raise ValueError(f"crop_segments_host: V, S_pad, D, P and T_out must be >= 1, got {(V, S_pad, D, P, T_out)}")
+    out = torch.full((P, T_out, D), float(pad_value), dtype=torch.float32)
+    lengths, los = torch.zeros(P, dtype=torch.int32), torch.zeros(P, dtype=torch.int32)
+    status = torch.zeros(2, dtype=torch.int32)
+    for p in range(P):
+        v = int(seg_video[p])
+        lo = n = 0
+        defined = 0 <= v < V and 0 <= int(src_len[v]) <= S_pad
+        if defined:
+            lo, n, defined = crop_rows(src_len[v], seg_times[p, 0], seg_times[p, 1], durations[v])
+        lengths[p], los[p] = n, lo
+        status[0] += int(n > T_out)
+        status[1] += int(not defined)
+        if n:
+            out[p, :min(n, T_out)] = src[v, lo:lo + min(n, T_out)]
+        else:
+            out[p, :1] = 0.0
+    return out, lengths, los, status
 
 
 # ---- the reference's per-clip functions under their own names and signatures (captioning_datasets/load_features.py), for

@@ -1334,3 +1334,41 @@ def proposal_select(predictions, durations, k, nms_tiou=None):
                                                  -1.0 if nms_tiou is None else float(nms_tiou), props.data_ptr(),
                                                  count.data_ptr(), _p(ws), words, stream()), "bmhrl_proposal_select")
     return props, count
+
+
+# ---- segment crop: the rows of temporal segments out of device-resident full-length stacks (csrc/segment_crop.hip)
+def crop_segments(src, src_len, durations, seg_video, seg_times, pad_value, T_out, out=None):
+    """crop and pad P segments out of the full-length stacks of V videos (see bmhrl_crop_segments): src (V, S_pad, D) fp32,
+    src_len (V) int32 true row counts, durations (V) float64 seconds, seg_video (P) int32, seg_times (P, 2) float64 [start,
+    end].  Returns out (P, T_out, D) fp32, lengths (P) int32 (the crop's row count, not clipped to T_out), lo (P) int32 (its
+    first row) and status (2) int32 = [segments longer than T_out, segments without a defined crop], all on the device;
+    nothing is read back.  `out`: a contiguous (P, T_out, D) fp32 tensor to fill instead of a new one."""
+    _need_cuda(src, src_len, durations, seg_video, seg_times, out)
+    if src.dim() != 3 or seg_times.dim() != 2:
+        raise ValueError("crop_segments: src (V, S_pad, D) and seg_times (P, 2) expected")
+    V, S_pad, D = src.shape
+    P, T_out = seg_times.shape[0], int(T_out)
+    if min(V, S_pad, D, P, T_out) < 1:
+        raise ValueError(f"crop_segments: V, S_pad, D, P and T_out must be >= 1, got {(V, S_pad, D, P, T_out)}")
+    _f32c(src, (V, S_pad, D), "crop_segments (src)")
+    for t, dtype, shape, what in ((src_len, torch.int32, (V,), "src_len"), (durations, torch.float64, (V,), "durations"),
+                                  (seg_video, torch.int32, (P,), "seg_video"), (seg_times, torch.float64, (P, 2), "seg_times")):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"crop_segments ({what}): expected a contiguous {dtype} tensor of shape {shape}")
+        if t.device != src.device:
+            raise ValueError(f"crop_segments ({what}): on {t.device}, src on {src.device}")
+    dev = src.device
+    if out is None:
+        out = torch.empty(P, T_out, D, device=dev)
+    else:
+        _f32c(out, (P, T_out, D), "crop_segments (out)")
+        if out.device != dev:
+            raise ValueError(f"crop_segments (out): on {out.device}, src on {dev}")
+    lengths = torch.empty(P, dtype=torch.int32, device=dev)
+    lo = torch.empty(P, dtype=torch.int32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().bmhrl_crop_segments(src.data_ptr(), src_len.data_ptr(), durations.data_ptr(), V, S_pad, D,
+                                               seg_video.data_ptr(), seg_times.data_ptr(), P, float(pad_value), T_out,
+                                               out.data_ptr(), lengths.data_ptr(), lo.data_ptr(), status.data_ptr(), stream()),
+               "bmhrl_crop_segments")
+    return out, lengths, lo, status

@@ -103,6 +103,47 @@ def postprocess_preds(model_output, cfg, batch):
     return trim_proposals(model_output, batch["duration_in_secs"])
 
 
+def device_proposal_rows(model_output, duration_in_secs, k, nms_tiou):
+    """ops.proposal_select on a device (B, N, 3) output -> (per video the surviving (start, end, conf) rows as Python lists,
+    rows considered per video), after ONE device-to-host copy"""
+    from . import ops
+    B = model_output.shape[0]
+    dur = torch.as_tensor(duration_in_secs, dtype=torch.float32).to(model_output.device, non_blocking=True)
+    k = int(k)
+    props, count = ops.proposal_select(model_output.detach().float().contiguous(), dur, k, nms_tiou)
+    packed = torch.cat([props.view(B, -1), count.view(B, 1).to(props.dtype)], dim=1).tolist()
+    return [[row[3 * j:3 * j + 3] for j in range(int(row[-1]))] for row in packed], min(k, model_output.shape[1])
+
+
+def select_rows(model_output, cfg, batch):
+    """(per video the (start, end, conf) rows that survive top-k, trimming and NMS, as Python lists; rows considered per
+    video): device input in one call of ops.proposal_select, anything else through the piecewise functions"""
+    from . import ops
+    on_device = model_output.is_cuda and 1 <= int(cfg.max_prop_per_vid) <= ops.PROPOSAL_MAX_K and \
+        1 <= model_output.shape[1] <= ops.PROPOSAL_MAX_N and model_output.shape[2] == 3
+    if on_device:
+        return device_proposal_rows(model_output, batch["duration_in_secs"], cfg.max_prop_per_vid, cfg.nms_tiou_thresh)
+    model_output = postprocess_preds(model_output, cfg, batch)
+    rows = []
+    for video_preds in model_output:
+        if cfg.nms_tiou_thresh is not None:
+            video_preds = non_max_suppresion(video_preds, cfg.nms_tiou_thresh)
+        rows.append(video_preds.tolist())
+    return rows, model_output.shape[1]
+
+
+def rows_to_segments(video_rows, shortest=0.2):
+    """one video's (start, end, conf) rows -> its entries of the submission dictionary: times and score rounded to 5 places,
+    segments of at most `shortest` seconds dropped (the reference's AnetPredictions.add_new_predictions)"""
+    vid_preds = []
+    for pred_start, pred_end, pred_conf in video_rows:
+        start, end = round(pred_start, 5), round(pred_end, 5)
+        if end - start > shortest:
+            # (the score is a one-element tuple in the reference: a trailing comma there; json writes it as a list)
+            vid_preds.append({"sentence": "", "proposal_score": (round(pred_conf, 5),), "timestamp": [start, end]})
+    return vid_preds
+
+
 class AnetPredictions:
     """collects a validation pass's proposals in the ActivityNet-captions submission layout (the reference's class of the
     same name: same dictionary, same counters, same file name)"""
@@ -116,42 +157,14 @@ class AnetPredictions:
         self.segments_total = 0
         self.num_vid_w_no_props = 0
 
-    def _device_rows(self, model_output, batch):
-        """per video the surviving (start, end, conf) rows as Python lists, after ONE device-to-host copy"""
-        from . import ops
-        B = model_output.shape[0]
-        dur = torch.as_tensor(batch["duration_in_secs"], dtype=torch.float32).to(model_output.device, non_blocking=True)
-        k = int(self.cfg.max_prop_per_vid)
-        props, count = ops.proposal_select(model_output.detach().float().contiguous(), dur, k, self.cfg.nms_tiou_thresh)
-        packed = torch.cat([props.view(B, -1), count.view(B, 1).to(props.dtype)], dim=1).tolist()
-        return [[row[3 * j:3 * j + 3] for j in range(int(row[-1]))] for row in packed], min(k, model_output.shape[1])
-
-    def _host_rows(self, model_output, batch):
-        model_output = postprocess_preds(model_output, self.cfg, batch)
-        rows = []
-        for video_preds in model_output:
-            if self.cfg.nms_tiou_thresh is not None:
-                video_preds = non_max_suppresion(video_preds, self.cfg.nms_tiou_thresh)
-            rows.append(video_preds.tolist())
-        return rows, model_output.shape[1]
-
     def add_new_predictions(self, model_output, batch):
         """model_output (B, N, 3) rows (centre s, length s, confidence).  Returns the proposals written per video."""
-        from . import ops
         B = model_output.shape[0]
-        on_device = model_output.is_cuda and 1 <= int(self.cfg.max_prop_per_vid) <= ops.PROPOSAL_MAX_K and \
-            1 <= model_output.shape[1] <= ops.PROPOSAL_MAX_N and model_output.shape[2] == 3
-        rows, k = self._device_rows(model_output, batch) if on_device else self._host_rows(model_output, batch)
+        rows, k = select_rows(model_output, self.cfg, batch)
         written = 0
-        shortest = 0.2      # seconds
         for b, video_rows in enumerate(rows):
-            vid_preds = []
-            for pred_start, pred_end, pred_conf in video_rows:
-                start, end = round(pred_start, 5), round(pred_end, 5)
-                if end - start > shortest:
-                    # (the score is a one-element tuple in the reference: a trailing comma there; json writes it as a list)
-                    vid_preds.append({"sentence": "", "proposal_score": (round(pred_conf, 5),), "timestamp": [start, end]})
-                    written += 1
+            vid_preds = rows_to_segments(video_rows)
+            written += len(vid_preds)
             if vid_preds:
                 self.predictions["results"][batch["video_ids"][b]] = vid_preds
             else:

@@ -922,6 +922,31 @@ int bmhrl_proposal_head(const float* x, const float* anchors, float cell_sec, in
 int bmhrl_proposal_select(const float* pred, int32_t B, int64_t N, const float* durations, int32_t k, float nms_tiou,
                           float* props, int32_t* count, uint64_t* workspace, int64_t workspace_elems, bmhrl_stream_t stream);
 
+/* ---- segment crop (csrc/segment_crop.hip) --------------------------------------------------------
+ * Cuts and pads the rows of P temporal segments out of full-length feature stacks that are resident on the device: the
+ * reference's crop_a_segment (captioning_datasets/load_features.py:14-35) and the padding of a batch of clips, without the
+ * feature files.  One ordinary launch on the caller's stream behind a one-wave launch that zeroes status; nothing is read
+ * back.
+ *
+ * src (V, S_pad, D) fp32 contiguous; src_len (V) int32: the true row count S of each video; durations (V) float64 seconds;
+ * seg_video (P) int32; seg_times (P, 2) float64 [start s, end s].  For segment p of video v, in IEEE float64 and in this
+ * order of operations (bmhrl_amd/loader.py crop_bounds):
+ *   a = trunc(S * (start / duration)), b = trunc(S * (end / duration))       (toward zero; limited to the int32 range)
+ *   if a == b: a -= 1 when a == S, else b += 1
+ *   (lo, hi) = Python's slice(a, b).indices(S): a negative end gets + S, then both are clamped to [0, S]
+ *   n = max(hi - lo, 0)
+ * Rows [0, min(n, T_out)) of out[p] (P, T_out, D) are src[v, lo + r]; the rows behind them hold pad_value; n == 0 gives one
+ * row of zeros and then pad_value (the loader's "missing clip").  lengths[p] = n, NOT clipped to T_out; lo[p] (optional) =
+ * lo, 0 where n == 0.  status[0] = number of segments with n > T_out (their first T_out rows are copied; nothing outside out
+ * is written); status[1] = number of segments without a defined crop, which are laid out as n == 0: seg_video outside [0, V),
+ * duration not > 0, a non-finite quotient or product, or src_len[v] outside [0, S_pad] (no row outside src is ever read).
+ * The counters are integer atomic adds of one thread per segment: exact in any order, the same with BMHRL_DETERMINISTIC.
+ * Every element of out is stored exactly once; 16-byte accesses when D % 4 == 0 and src and out are 16-byte aligned, 4-byte
+ * ones otherwise (any D >= 1).  -22 and nothing launched: a null pointer other than lo; V, P, D, T_out or S_pad < 1. */
+int bmhrl_crop_segments(const float* src, const int32_t* src_len, const double* durations, int32_t V, int32_t S_pad, int32_t D,
+                        const int32_t* seg_video, const double* seg_times, int32_t P, float pad_value, int32_t T_out,
+                        float* out, int32_t* lengths, int32_t* lo, int32_t* status, bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
