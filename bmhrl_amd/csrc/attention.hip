@@ -4,6 +4,8 @@
 #include "attention_fwd.h"
 
 void bmhrl_attn128_set_cfg(int code);   // attention128.hip
+int bmhrl_attn128_plan_fwd(int B, int H, int Sq, int Sk);
+int bmhrl_attn128_plan_bwd(int B, int H, int Sq, int Sk);
 // attention_fwd_sk256.hip: the two-phase exact-softmax form for memories of at most 256 keys
 bool bmhrl_attn256_sk_ok(int B, int H, int Sq, int Sk, long mask_sq, bool force);
 int bmhrl_attn256_sk_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* O, int64_t ldo,
@@ -103,6 +105,18 @@ extern "C" int bmhrl_attention_config(int32_t head_dim, int32_t code) {
   else if (head_dim == 128) bmhrl_attn128_set_cfg(code);
   else return -22;
   return 0;
+}
+
+extern "C" int bmhrl_attention_plan(int32_t kind, int32_t B, int32_t H, int32_t Sq, int32_t Sk, int64_t mask_sq) {
+  if (kind == 1) return mask_sq != 0 ? -22 : bmhrl_attn128_plan_fwd(B, H, Sq, Sk);      // (the shared form takes key masks only)
+  if (kind == 2) return mask_sq != 0 ? -22 : bmhrl_attn128_plan_bwd(B, H, Sq, Sk);
+  if (kind != 0 || B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0) return -22;
+  // head dimension 256, the decisions of bmhrl_attention_fwd and attention256_entry in their order
+  if ((g_cfg256 == 0 || g_cfg256 == 256) && bmhrl_attn256_sk_ok(B, H, Sq, Sk, mask_sq, g_cfg256 == 256)) return 256;
+  const int code = (g_cfg256 == 0 || g_cfg256 == 256) ? attn256_auto_code(B, H, Sq) : g_cfg256;
+  if (code != 41 && code != 22) return -22;
+  if (Sk > AttnCfg<256, 4, 1, 3, false>::MAX_SK || !attn_grid_ok(B, H, Sq, code / 10)) return -22;
+  return code;
 }
 
 extern "C" int bmhrl_attention_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,

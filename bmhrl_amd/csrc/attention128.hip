@@ -18,6 +18,24 @@ int g_cfg128 = 0;   // (QW, KW) split: 0 = automatic
 
 void bmhrl_attn128_set_cfg(int code) { g_cfg128 = code; }
 
+// bmhrl_attention_plan (attention.hip), kinds 128-fwd and 128-bwd: the code the entries below take for a shape the argument
+// checks accept, -22 for one they refuse
+int bmhrl_attn128_plan_fwd(int B, int H, int Sq, int Sk) {
+  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0) return -22;
+  const bool pair_served = bmhrl_attn128_pair_ok(B, H, Sq, Sk);
+  const int code = g_cfg128 != 0 ? g_cfg128 : attn128_auto_code(B, H, Sq, Sk, pair_served);
+  if (code == 14) return pair_served ? 14 : -22;
+  if (code != 41 && code != 22 && code != 24) return -22;
+  if (Sk > AttnCfg<128, 4, 1, 4, true>::MAX_SK || !attn_grid_ok(B, H, Sq, code / 10)) return -22;
+  return code;
+}
+int bmhrl_attn128_plan_bwd(int B, int H, int Sq, int Sk) {
+  if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || Sk > AttnCfg<128, 4, 1, 4, true>::MAX_SK) return -22;
+  const bool wide = attn128_bwd_wide(B, H, Sq);
+  if (!attn_grid_ok(B, H, Sq, wide ? 4 : 2)) return -22;
+  return wide ? 41 : 22;
+}
+
 extern "C" int bmhrl_attention_shared128_fwd(const void* Qp, int64_t ldq, const void* X, int64_t ldx, void* ctx, int64_t ldo,
                                              float* row_max, float* row_sum, const uint8_t* mask, int64_t mask_sb,
                                              int32_t B, int32_t H, int32_t Sq, int32_t Sk, float scale,
@@ -49,9 +67,7 @@ extern "C" int bmhrl_attention_shared128_bwd(const void* Qp, int64_t ldq, const 
   a.row_max = row_max; a.row_sum = row_sum; a.delta = delta; a.mask = mask; a.mask_sb = mask_sb;
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.scale = scale;
   hipStream_t s = (hipStream_t)stream;
-  // dQp: the forward's query-block split (4 x 1 with two workgroups per CU when there are enough 32-row blocks, else 2 x 2)
-  const int64_t rows32 = (int64_t)B * H * ((Sq + 31) / 32);
-  const bool wide = rows32 >= 1536;
+  const bool wide = attn128_bwd_wide(B, H, Sq);      // dQp: 4 x 1 or 2 x 2 query blocks x key splits
   const int qw = wide ? 4 : 2;
   if (Sk > AttnCfg<DK, 4, 1, 4, true>::MAX_SK) return -22;
   a.q_tiles = (Sq + 32 * qw - 1) / (32 * qw);

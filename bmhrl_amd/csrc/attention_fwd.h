@@ -1029,6 +1029,33 @@ hipError_t launch_attn(AttnArgs a, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// ---- the automatic choices of the entries below, as host functions of their own: bmhrl_attention_plan (attention.hip)
+// reports what an entry would launch through the very functions the entry calls.
+// head dimension 256: 4 x 1 (128 query rows per workgroup, every wave sees every key: no merge, K fragments requested across
+// the barrier) as soon as that gives most CUs a workgroup; else 2 x 2 (64 rows, two key halves).  Measured on MI355X at B16 H4
+// (tests/kbench/attn_bench time): Sq800 Sk256 35.0 vs 47.5 us, Sq256 Sk256 17.4 vs 14.4 us, Sq256 Sk800 36 vs 28 us.
+inline int attn256_auto_code(int B, int H, int Sq) { return ((int64_t)B * H * ((Sq + 127) / 128) >= 200) ? 41 : 22; }
+// head dimension 128, forward: 4 x 1 (128 query rows per workgroup, two workgroups per CU) when there are enough 32-row query
+// blocks to give every SIMD two waves that way; else 2 x 2 (64 rows, two key halves).  Both request the K fragments of the
+// next tile across the barrier (four stages of the shared image).  Measured on MI355X at B16 H4 (tests/kbench/attn_bench
+// time): Sq800 Sk800 30.4 vs 34.9 us, Sq256 Sk800 20.2 vs 14.3 us; eight waves (2 x 4) lose to 2 x 2 on every shape tried.
+// The pair form (attention_pair.h: 64 slots x 4 key splits per workgroup, no barrier in the loop) when its workgroups fill
+// the chip in one round and a key split has at least two tiles -- the shape of BASELINE configs[1]'s V<-A attention.
+// (pair_served: the translation unit links the pair form and it serves the shape)
+inline int attn128_auto_code(int B, int H, int Sq, int Sk, bool pair_served) {
+  const int64_t rows32 = (int64_t)B * H * ((Sq + 31) / 32);      // 32-row query blocks
+  const bool pair = pair_served && rows32 <= 2 * 304 && Sk >= 256 && g_attn_pair_on;
+  return pair ? 14 : (rows32 >= 1536 ? 41 : 22);
+}
+// head dimension 128, backward (dQp): the forward's query-block split -- 4 x 1 with two workgroups per CU when there are
+// enough 32-row blocks ("wide", reported as 41), else 2 x 2 ("narrow", 22)
+inline bool attn128_bwd_wide(int B, int H, int Sq) { return (int64_t)B * H * ((Sq + 31) / 32) >= 1536; }
+// the grid of a QW-block launch fits the workgroup map's 32-bit divisions (launch_attn, bmhrl_attention_shared128_bwd)
+inline bool attn_grid_ok(int B, int H, int Sq, int QW) {
+  const int64_t q_tiles = (Sq + 32 * QW - 1) / (32 * QW);
+  return (int64_t)B * H * q_tiles * H * q_tiles < (1ll << 32);
+}
+
 // ---- entry bodies shared by the bf16 and the fp16 translation units (the extern "C" symbols differ, the kernels do not).
 // Templates, so that a translation unit only instantiates the kernels of the entry it defines.
 template <int UNUSED = 0>
@@ -1052,10 +1079,7 @@ int attention256_entry(const void* Q, int64_t ldq, const void* K, int64_t ldk, c
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.scale = scale; a.dropout_p = dropout_p; a.seed = seed; a.seed_dev = seed_dev;
   a.k_hs = DK; a.v_hs = DK;
   a.dbg = g_attn_dbg;
-  // 4 x 1 (128 query rows per workgroup, every wave sees every key: no merge, K fragments requested across the barrier)
-  // as soon as that gives most CUs a workgroup; else 2 x 2 (64 rows, two key halves).  Measured on MI355X at B16 H4
-  // (tests/kbench/attn_bench time): Sq800 Sk256 35.0 vs 47.5 us, Sq256 Sk256 17.4 vs 14.4 us, Sq256 Sk800 36 vs 28 us.
-  if (code == 0) code = ((int64_t)B * H * ((Sq + 127) / 128) >= 200) ? 41 : 22;
+  if (code == 0) code = attn256_auto_code(B, H, Sq);
   hipError_t e;
   if (code == 41) e = launch_attn<DK, 4, 1, 3, false, true>(a, stream);
   else if (code == 22) e = launch_attn<DK, 2, 2, 2, false, false>(a, stream);
@@ -1088,17 +1112,7 @@ int attention128_entry(const void* Qp, int64_t ldq, const void* X, int64_t ldx, 
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.scale = scale; a.dropout_p = 0.f; a.seed = 0; a.seed_dev = nullptr;
   a.k_hs = 0; a.v_hs = 0;                       // one 128-wide key / value row for every head
   a.dbg = g_attn_dbg;
-  // 4 x 1 (128 query rows per workgroup, two workgroups per CU) when there are enough 32-row query blocks to give every
-  // SIMD two waves that way; else 2 x 2 (64 rows, two key halves).  Both request the K fragments of the next tile across
-  // the barrier (four stages of the shared image).  Measured on MI355X at B16 H4 (tests/kbench/attn_bench time):
-  // Sq800 Sk800 30.4 vs 34.9 us, Sq256 Sk800 20.2 vs 14.3 us; eight waves (2 x 4) lose to 2 x 2 on every shape tried.
-  // The pair form (attention_pair.h: 64 slots x 4 key splits per workgroup, no barrier in the loop) when its workgroups fill
-  // the chip in one round and a key split has at least two tiles -- the shape of BASELINE configs[1]'s V<-A attention.
-  if (code == 0) {
-    const int64_t rows32 = (int64_t)B * H * ((Sq + 31) / 32);      // 32-row query blocks
-    const bool pair = pair_fn != nullptr && pair_ok(B, H, Sq, Sk) && rows32 <= 2 * 304 && Sk >= 256 && g_attn_pair_on;
-    code = pair ? 14 : (rows32 >= 1536 ? 41 : 22);
-  }
+  if (code == 0) code = attn128_auto_code(B, H, Sq, Sk, pair_fn != nullptr && pair_ok(B, H, Sq, Sk));
   if (code == 14) {
     if (pair_fn == nullptr || !pair_ok(B, H, Sq, Sk)) return -22;
     return pair_fn(Qp, ldq, X, ldx, ctx, ldo, row_max, row_sum, mask, mask_sb, B, H, Sq, Sk, scale, stream);

@@ -19,6 +19,15 @@ def attention_max_keys() -> int:
     return _lib.load().bmhrl_attention_max_keys()
 
 
+ATTN_PLAN_KINDS = {"256-fwd": 0, "128-fwd": 1, "128-bwd": 2}
+
+
+def attention_plan(kind: str, B: int, H: int, Sq: int, Sk: int, mask_sq: int = 0) -> int:
+    """the kernel code the entry `kind` would take for this shape under the current bmhrl_attention_config pin (pure host
+    query: bmhrl_attention_plan); negative for a shape the entry refuses"""
+    return int(_lib.load().bmhrl_attention_plan(ATTN_PLAN_KINDS[kind], B, H, Sq, Sk, mask_sq))
+
+
 def pad8(n: int) -> int:
     return (n + 7) & ~7
 

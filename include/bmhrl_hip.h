@@ -164,9 +164,17 @@ int bmhrl_attention_max_keys(void);
 /* Tuning aid: pin the (query blocks x key splits) shape of the attention workgroups -- head_dim 256 or 128; code = 10 * QW + KW
  * (41: 4 x 1, 22: 2 x 2; head_dim 256 also 256: the two-phase exact-softmax kernel for at most 256 keys, which the automatic
  * choice takes when the grid fills the chip; head_dim 128 also 24: 2 x 4 and 14: the r04 form in which one wave carries two heads over four key
- * splits, shapes it does not serve fall back to the automatic choice), 0 = automatic (the default).  Process-wide, not
+ * splits; a shape it does not serve -- an odd head count -- is refused while it is pinned), 0 = automatic (the default).  Process-wide, not
  * thread-safe; results do not depend on it beyond bf16 rounding of P. */
 int bmhrl_attention_config(int32_t head_dim, int32_t code);
+
+/* Which kernel an attention entry would launch for a shape under the current bmhrl_attention_config pin (pure host query, no
+ * launch; the entries take their automatic choices through the same functions).  kind 0: bmhrl_attention_fwd (256, 41 or
+ * 22); kind 1: bmhrl_attention_shared128_fwd (14, 41, 22 or 24); kind 2: bmhrl_attention_shared128_bwd (41: the wide dQp
+ * kernel, 22: the narrow one; it has no pin).  mask_sq as passed to the entry (0: key mask or none).  < 0 for a shape the
+ * entry refuses (Sk above bmhrl_attention_max_keys, a pinned 14 with an odd head count, ...).  The fp16 entries have no pin:
+ * they take what this reports with the pin at 0, except that they have no two-phase kernel (41 or 22 in place of 256). */
+int bmhrl_attention_plan(int32_t kind, int32_t B, int32_t H, int32_t Sq, int32_t Sk, int64_t mask_sq);
 
 /* Attention core of SHORT sequences (Sq, Sk <= 32; d_k in {64, 128, 256, 512}) as one launch per direction: the caption
  * self attention of the fusion layers and the worker's goal attention (model/multihead_attention.py:7-31 on the 30 caption
