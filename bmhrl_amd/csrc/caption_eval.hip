@@ -23,26 +23,15 @@
 
 #pragma clang fp contract(off)
 
+#include "caption_text.h"                // kMaxL, kMaxR, kMaxN, gram_eq (shared with rewards.hip), group_of (with soda.hip)
+
 #define S_(x) ((hipStream_t)(x))
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxL = BMHRL_REWARDS_MAX_L;
-constexpr int kMaxR = BMHRL_REWARDS_MAX_R;
-constexpr int kMaxN = 4;
 constexpr int kInts = BMHRL_CAPTION_EVAL_PAIR_INTS;
 constexpr int kOuts = BMHRL_CAPTION_EVAL_GROUP_SCORES;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// words a[0, k) == b[0, k): all four words are read (the word arrays carry 4 words of padding), no early exit
-__device__ __forceinline__ bool gram_eq(const int* a, const int* b, int k) {
-  bool eq = true;
-#pragma unroll
-  for (int q = 0; q < kMaxN; ++q) eq &= q >= k || a[q] == b[q];
-  return eq;
-}
 
 // the number of pairs in [g0, g1) whose reference holds the gram a[0, k).  Word ids are >= 0; the window behind a
 // reference's end holds -1, so a gram never matches across it.  q and j are the same in every lane.
@@ -84,14 +73,10 @@ __global__ __launch_bounds__(kThreads) void caption_pair_kernel(
 
   const int p = blockIdx.x, tid = threadIdx.x;
   const int M = clampi(hyp_len[p], 0, L), Rb = clampi(ref_len[p], 0, R);
-  if (tid == 0) {                           // the group of this pair: the last g with group_off[g] <= p
-    int lo = 0, hi = G - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (group_off[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    s_g0 = clampi(group_off[lo], 0, P);
-    s_g1 = clampi(group_off[lo + 1], 0, P);
+  if (tid == 0) {
+    const int g = group_of(group_off, G, p);  // the group of this pair
+    s_g0 = clampi(group_off[g], 0, P);
+    s_g1 = clampi(group_off[g + 1], 0, P);
     s_lcs = 0;
   }
   if (tid < kMaxN) s_hw[M + tid] = s_rw[Rb + tid] = -1;

@@ -54,6 +54,13 @@ static inline bool bmhrl_deterministic() {
   return on;
 }
 
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// candidate order of the decoders' selections: value descending, ties to the smaller index (a stable sort of -value)
+__device__ __forceinline__ bool beats(float sa, int ia, float sb, int ib) {
+  return sa > sb || (sa == sb && ia < ib);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -29,7 +29,7 @@
 
 #pragma clang fp contract(off)
 
-#include "meteor_align.h"                // take_highest / match_stage / align_prefix, shared with soda.hip
+#include "meteor_align.h"                // align_prefix and, through caption_text.h, the staging and the score: shared with soda.hip
 
 #define S_(x) ((hipStream_t)(x))
 
@@ -43,47 +43,22 @@ __global__ __launch_bounds__(kThreads) void meteor_kernel(
     const int32_t* __restrict__ syn_off, const int32_t* __restrict__ syn_ids, int n_syn, const int32_t* __restrict__ ref,
     const int32_t* __restrict__ ref_stem, long ldr, const int32_t* __restrict__ ref_len, double alpha, double beta,
     double gamma, int L, int R, double* __restrict__ scores, long lds, float* __restrict__ delta, long ldd) {
-  __shared__ int s_tw[kMaxL], s_ts[kMaxL], s_tb[kMaxL], s_te[kMaxL];   // per token: word id (-1: none), stem id, synonym row
-  __shared__ int s_mc[kMaxL];            // words among tokens [0, t]
-  __shared__ int s_hw[kMaxL], s_hs[kMaxL], s_hb[kMaxL], s_he[kMaxL];   // the same of the compacted hypothesis words
+  __shared__ HypWords s_h;                                // the tokens and the compacted hypothesis words (caption_text.h)
   __shared__ int s_rw[kMaxR], s_rs[kMaxR];                // the reference: word ids, stem ids
   __shared__ u64 s_syn[kMaxL][kQ];                        // reference positions the synonym test of word h selects
   __shared__ double s_score[kMaxL + 1];
 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
-  int Rb = ref_len[b];
-  Rb = Rb < 0 ? 0 : (Rb > R ? R : Rb);
-  for (int t = tid; t < L; t += kThreads) {     // everything a token brings along, so that the tables are read once
-    const long v = (long)hyp[(size_t)b * ldh + t];
-    const bool ok = v >= 0 && v < V;
-    s_tw[t] = ok ? vmap[v] : -1;
-    s_ts[t] = ok && vstem ? vstem[v] : -1;
-    int beg = ok && syn_off ? syn_off[v] : 0, end = ok && syn_off ? syn_off[v + 1] : 0;
-    beg = beg < 0 ? 0 : beg;
-    end = end > n_syn ? n_syn : end;
-    s_tb[t] = beg;
-    s_te[t] = end;
-  }
+  const int Rb = clampi(ref_len[b], 0, R);
   for (int r = tid; r < Rb; r += kThreads) {
     s_rw[r] = ref[(size_t)b * ldr + r];
     s_rs[r] = vstem ? ref_stem[(size_t)b * ldr + r] : -1;
   }
   if (tid == 0) s_score[0] = 0.0;
-  __syncthreads();
-  for (int t = tid; t < L; t += kThreads) {
-    int c = 0;
-    for (int j = 0; j <= t; ++j) c += s_tw[j] >= 0;
-    s_mc[t] = c;
-    if (s_tw[t] >= 0) {
-      s_hw[c - 1] = s_tw[t];
-      s_hs[c - 1] = s_ts[t];
-      s_hb[c - 1] = s_tb[t];
-      s_he[c - 1] = s_te[t];
-    }
-  }
-  __syncthreads();
-  const int M = __builtin_amdgcn_readfirstlane(s_mc[L - 1]);
+  // (the helper's first barrier covers the reference words and s_score[0] above)
+  stage_hyp_words(s_h, hyp + (size_t)b * ldh, L, kThreads, vmap, vstem, V, syn_off, n_syn);
+  const int M = __builtin_amdgcn_readfirstlane(s_h.mc[L - 1]);
   const int nq = (Rb + WAVE - 1) / WAVE;
 
   // this lane's reference positions (those behind the reference start out used) and hypothesis words
@@ -100,24 +75,24 @@ __global__ __launch_bounds__(kThreads) void meteor_kernel(
 #pragma unroll
   for (int p = 0; p < kP; ++p) {
     const int h = p * WAVE + lane;
-    hw[p] = h < M ? s_hw[h] : -1;
-    hs[p] = h < M ? s_hs[h] : -1;
+    hw[p] = h < M ? s_h.hw[h] : -1;
+    hs[p] = h < M ? s_h.hs[h] : -1;
   }
 
   if (syn_off && Rb > 0) {
     // 64 ids of a row per load, one per lane; the first load of the wave's next word is in flight while this one is searched
     int nbeg = 0, nend = 0, nmine = -1;
     if (wave < M) {
-      nbeg = __builtin_amdgcn_readfirstlane(s_hb[wave]);
-      nend = __builtin_amdgcn_readfirstlane(s_he[wave]);
+      nbeg = __builtin_amdgcn_readfirstlane(s_h.hb[wave]);
+      nend = __builtin_amdgcn_readfirstlane(s_h.he[wave]);
       nmine = nbeg + lane < nend ? syn_ids[nbeg + lane] : -1;
     }
     for (int h = wave; h < M; h += kWaves) {
-      const int w = __builtin_amdgcn_readfirstlane(s_hw[h]), beg = nbeg, end = nend;
+      const int w = __builtin_amdgcn_readfirstlane(s_h.hw[h]), beg = nbeg, end = nend;
       int mine = nmine;
       if (h + kWaves < M) {
-        nbeg = __builtin_amdgcn_readfirstlane(s_hb[h + kWaves]);
-        nend = __builtin_amdgcn_readfirstlane(s_he[h + kWaves]);
+        nbeg = __builtin_amdgcn_readfirstlane(s_h.hb[h + kWaves]);
+        nend = __builtin_amdgcn_readfirstlane(s_h.he[h + kWaves]);
         nmine = nbeg + lane < nend ? syn_ids[nbeg + lane] : -1;
       }
       bool hit[kQ];
@@ -151,16 +126,7 @@ __global__ __launch_bounds__(kThreads) void meteor_kernel(
         align_prefix<1>(m, nq, lane, vstem != nullptr, syn_off != nullptr, hw, hs, s_syn, rw, rs, used0, matches, chunks);
       else
         align_prefix<kQ>(m, nq, lane, vstem != nullptr, syn_off != nullptr, hw, hs, s_syn, rw, rs, used0, matches, chunks);
-      if (matches > 0) {
-        const double p = (double)matches / (double)m, r = (double)matches / (double)Rb;
-        const double den = alpha * p + (1.0 - alpha) * r;
-        if (den != 0.0) {
-          const double fmean = (p * r) / den;
-          const double frag = (double)chunks / (double)matches;
-          const double penalty = gamma * pow(frag, beta);
-          score = (1.0 - penalty) * fmean;
-        }
-      }
+      score = meteor_score(matches, chunks, m, Rb, alpha, beta, gamma);
     }
     if (lane == 0) s_score[m] = score;
   }
@@ -169,9 +135,9 @@ __global__ __launch_bounds__(kThreads) void meteor_kernel(
   // the row over token positions: a token that yields no word repeats the score before it.  The reference keeps the row
   // in float32, so the differences are taken in float32.
   for (int t = tid; t < L; t += kThreads) {
-    const double cur = s_score[s_mc[t]];
+    const double cur = s_score[s_h.mc[t]];
     scores[(size_t)b * lds + t] = cur;
-    delta[(size_t)b * ldd + t] = t == 0 ? (float)cur : (float)cur - (float)s_score[s_mc[t - 1]];
+    delta[(size_t)b * ldd + t] = t == 0 ? (float)cur : (float)cur - (float)s_score[s_h.mc[t - 1]];
   }
 }
 

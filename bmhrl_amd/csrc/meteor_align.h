@@ -11,13 +11,12 @@
 //
 // Include it after common.h and include/bmhrl_hip.h, inside a file that has set `#pragma clang fp contract(off)`.
 #pragma once
+#include "caption_text.h"                // kMaxL, kMaxR; the stages around the alignment
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int kMaxL = BMHRL_REWARDS_MAX_L;
-constexpr int kMaxR = BMHRL_REWARDS_MAX_R;
 constexpr int kQ = kMaxR / WAVE;       // reference positions per lane
 constexpr int kP = kMaxL / WAVE;       // hypothesis words per lane
 static_assert(kMaxR % WAVE == 0 && kMaxL % WAVE == 0 && kQ <= 32, "the used bits of a lane are one word");

@@ -25,14 +25,13 @@
 
 #pragma clang fp contract(off)
 
+#include "caption_text.h"                // kMaxL, kMaxR, kMaxN, gram_eq: shared with caption_eval.hip
+
 #define S_(x) ((hipStream_t)(x))
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxL = BMHRL_REWARDS_MAX_L;
-constexpr int kMaxR = BMHRL_REWARDS_MAX_R;
-constexpr int kMaxN = 4;
 
 // the host's hash of a key of 4 word ids (bmhrl_amd/rewards.py _hash): uint32 arithmetic, wrap-around
 __device__ __forceinline__ uint32_t gram_hash(const int32_t* w) {
@@ -61,14 +60,6 @@ __device__ double gram_log_df(const int32_t* words, int k, const int32_t* __rest
   return 0.0;
 }
 
-// words a[0, k) == b[0, k): all four words are read (the word arrays carry 3 words of padding), no early exit
-__device__ __forceinline__ bool gram_eq(const int* a, const int* b, int k) {
-  bool eq = true;
-#pragma unroll
-  for (int q = 0; q < kMaxN; ++q) eq &= q >= k || a[q] == b[q];
-  return eq;
-}
-
 __global__ __launch_bounds__(kThreads) void rewards_kernel(
     const int64_t* __restrict__ hyp, long ldh, const int32_t* __restrict__ vmap, int V, long eos,
     const int32_t* __restrict__ ref, long ldr, const int32_t* __restrict__ ref_len, const int32_t* __restrict__ df_keys,
@@ -89,8 +80,7 @@ __global__ __launch_bounds__(kThreads) void rewards_kernel(
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const bool cider = metric == BMHRL_REWARD_CIDER;
-  int Rb = ref_len[b];
-  Rb = Rb < 0 ? 0 : (Rb > R ? R : Rb);
+  const int Rb = clampi(ref_len[b], 0, R);
   if (tid == 0) s_eos = L;
   if (tid < kMaxN) s_hw[kMaxL + tid] = s_rw[kMaxR + tid] = -1;
   __syncthreads();

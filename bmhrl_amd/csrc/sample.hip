@@ -47,8 +47,6 @@ __device__ __forceinline__ unsigned order_key(float x) {
 
 __device__ __forceinline__ float q_of(float x, float M, float temperature) { return expf((x - M) / temperature); }
 
-__device__ __forceinline__ bool beats(float a, int ia, float b, int ib) { return a > b || (a == b && ia < ib); }
-
 // inclusive wave scan (fixed order), then the exclusive block offset of this lane; *total: the block sum
 __device__ __forceinline__ float block_excl_scan(float v, SampleSmem& sm, float* total) {
   const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;

@@ -38,16 +38,6 @@ constexpr int kDpWaves = 4;                          // DP launch: (group, thres
 constexpr int kDpQ = BMHRL_SODA_MAX_REFS / WAVE;     // references per lane
 static_assert(BMHRL_SODA_MAX_REFS % WAVE == 0, "whole waves of references");
 
-// the last g in [0, G) with off[g] <= x (off ascends from 0; x < off[G])
-__device__ __forceinline__ int group_of(const int32_t* __restrict__ off, int G, int x) {
-  int lo = 0, hi = G - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(kRowThreads) void meteor_matrix_kernel(
     const int64_t* __restrict__ hyp, long ldh, const int32_t* __restrict__ vmap, const int32_t* __restrict__ vstem, int V,
     const int32_t* __restrict__ syn_off, const int32_t* __restrict__ syn_ids, int n_syn, const int32_t* __restrict__ ref,
@@ -55,41 +45,15 @@ __global__ __launch_bounds__(kRowThreads) void meteor_matrix_kernel(
     const int32_t* __restrict__ hyp_idx, const int32_t* __restrict__ ref_idx, const int32_t* __restrict__ hyp_off,
     const int32_t* __restrict__ ref_off, const int64_t* __restrict__ cell_off, int G, double alpha, double beta, double gamma,
     double* __restrict__ S) {
-  __shared__ int s_tw[kMaxL], s_ts[kMaxL], s_tb[kMaxL], s_te[kMaxL];   // per token: word id (-1: none), stem id, synonym row
-  __shared__ int s_mc[kMaxL];            // words among tokens [0, t]
-  __shared__ int s_hw[kMaxL], s_hs[kMaxL], s_hb[kMaxL], s_he[kMaxL];   // the same of the compacted hypothesis words
+  __shared__ HypWords s_h;               // the tokens and the compacted hypothesis words (caption_text.h)
   __shared__ int s_g;
   extern __shared__ __attribute__((aligned(16))) u64 s_syn_all[];      // per wave: (L, kQ) synonym masks of the current cell
 
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), nthreads = blockDim.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE), nwaves = nthreads / WAVE;
   if (tid == 0) s_g = group_of(hyp_off, G, row);
-  const size_t hrow = (size_t)hyp_idx[row] * ldh;
-  for (int t = tid; t < L; t += nthreads) {     // everything a token brings along, so that the tables are read once
-    const long v = (long)hyp[hrow + t];
-    const bool ok = v >= 0 && v < V;
-    s_tw[t] = ok ? vmap[v] : -1;
-    s_ts[t] = ok && vstem ? vstem[v] : -1;
-    int beg = ok && syn_off ? syn_off[v] : 0, end = ok && syn_off ? syn_off[v + 1] : 0;
-    beg = beg < 0 ? 0 : beg;
-    end = end > n_syn ? n_syn : end;
-    s_tb[t] = beg;
-    s_te[t] = end;
-  }
-  __syncthreads();
-  for (int t = tid; t < L; t += nthreads) {
-    int c = 0;
-    for (int j = 0; j <= t; ++j) c += s_tw[j] >= 0;
-    s_mc[t] = c;
-    if (s_tw[t] >= 0) {
-      s_hw[c - 1] = s_tw[t];
-      s_hs[c - 1] = s_ts[t];
-      s_hb[c - 1] = s_tb[t];
-      s_he[c - 1] = s_te[t];
-    }
-  }
-  __syncthreads();
-  const int M = __builtin_amdgcn_readfirstlane(s_mc[L - 1]);
+  stage_hyp_words(s_h, hyp + (size_t)hyp_idx[row] * ldh, L, nthreads, vmap, vstem, V, syn_off, n_syn);
+  const int M = __builtin_amdgcn_readfirstlane(s_h.mc[L - 1]);
   const int g = __builtin_amdgcn_readfirstlane(s_g);
   const int r0 = ref_off[g], Rg = ref_off[g + 1] - r0;
   double* out = S + cell_off[g] + (long)(row - hyp_off[g]) * Rg;
@@ -98,16 +62,15 @@ __global__ __launch_bounds__(kRowThreads) void meteor_matrix_kernel(
 #pragma unroll
   for (int p = 0; p < kP; ++p) {
     const int h = p * WAVE + lane;
-    hw[p] = h < M ? s_hw[h] : -1;
-    hs[p] = h < M ? s_hs[h] : -1;
+    hw[p] = h < M ? s_h.hw[h] : -1;
+    hs[p] = h < M ? s_h.hs[h] : -1;
   }
   u64 (*syn)[kQ] = (u64 (*)[kQ])(s_syn_all + (size_t)wave * L * kQ);
 
   // no workgroup barrier below: the waves run different numbers of cells
   for (int j = wave; j < Rg; j += nwaves) {
     const size_t rrow = (size_t)ref_idx[r0 + j] * ldr;
-    int Rb = ref_len[ref_idx[r0 + j]];
-    Rb = __builtin_amdgcn_readfirstlane(Rb < 0 ? 0 : (Rb > R ? R : Rb));
+    const int Rb = __builtin_amdgcn_readfirstlane(clampi(ref_len[ref_idx[r0 + j]], 0, R));
     const int nq = (Rb + WAVE - 1) / WAVE;
     // this lane's reference positions (those behind the reference start out used)
     int rw[kQ], rs[kQ];
@@ -124,7 +87,7 @@ __global__ __launch_bounds__(kRowThreads) void meteor_matrix_kernel(
     if (M > 0 && Rb > 0) {
       if (syn_off) {
         for (int h = 0; h < M; ++h) {           // 64 ids of the word's row per load, one per lane
-          const int w = s_hw[h], beg = s_hb[h], end = s_he[h];
+          const int w = s_h.hw[h], beg = s_h.hb[h], end = s_h.he[h];
           bool hit[kQ];
 #pragma unroll
           for (int q = 0; q < kQ; ++q) hit[q] = rw[q] == w;
@@ -152,16 +115,7 @@ __global__ __launch_bounds__(kRowThreads) void meteor_matrix_kernel(
         align_prefix<1>(M, nq, lane, vstem != nullptr, syn_off != nullptr, hw, hs, syn, rw, rs, used0, matches, chunks);
       else
         align_prefix<kQ>(M, nq, lane, vstem != nullptr, syn_off != nullptr, hw, hs, syn, rw, rs, used0, matches, chunks);
-      if (matches > 0) {                         // the operations of meteor.hip, in its order
-        const double p = (double)matches / (double)M, r = (double)matches / (double)Rb;
-        const double den = alpha * p + (1.0 - alpha) * r;
-        if (den != 0.0) {
-          const double fmean = (p * r) / den;
-          const double frag = (double)chunks / (double)matches;
-          const double penalty = gamma * pow(frag, beta);
-          score = (1.0 - penalty) * fmean;
-        }
-      }
+      score = meteor_score(matches, chunks, M, Rb, alpha, beta, gamma);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");       // the masks are read before the next cell rewrites them
     }
     if (lane == 0) out[j] = score;

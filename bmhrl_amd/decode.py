@@ -867,7 +867,7 @@ def _group_beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality,
 
 
 class GroupBeamDecoder(BeamDecoder):
-    """BeamDecoder with bmhrl_group_beam_select (csrc/group_beam.hip: rules G2-G4 for all groups, one launch) in place of
+    """BeamDecoder with bmhrl_group_beam_select (csrc/beam.hip, the grouped select: rules G2-G4 for all groups, one launch) in place of
     bmhrl_beam_select; the two reorder launches, the per-beam buffers, the constraints launch and the result are
     BeamDecoder's, so the token step has no launch more than plain beam search.  beam_groups / diversity_penalty are launch
     arguments: set_params() captures the step again when they change, as SampleDecoder's.  A decoder from for_batch starts

@@ -780,6 +780,22 @@ BEAM_MAX = 16                       # largest beam of bmhrl_beam_select
 BEAM_REORDER_CHUNK = 256 * 16 * 4   # bytes of one (buffer, row) a reorder workgroup moves
 
 
+def _check_select_buffers(fn, need, K, G, V, ld, logp, scores, scores_out, finished, finished_out, parent, tok, hist, t,
+                          last_live, R):
+    """the conditions beam_select (G = 1) and group_beam_select share; need: how fn's message words K' = K / G <= V"""
+    if not (1 <= K <= BEAM_MAX and G >= 1 and K % G == 0 and K // G <= V and ld >= V and logp.dtype == torch.float32
+            and logp.numel() >= (R - 1) * ld + V):
+        raise ValueError(f"{fn}: need 1 <= K <= 16, {need} and fp32 logp rows (B*K, ld >= V)")
+    for x, dt in ((scores, torch.float32), (scores_out, torch.float32), (finished, torch.uint8), (finished_out, torch.uint8),
+                  (parent, torch.int32), (tok, torch.int64)):
+        if x.dtype != dt or x.numel() < R or not x.is_contiguous():
+            raise ValueError(f"{fn}: expected a contiguous {dt} buffer of {R} elements")
+    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != R or hist.stride(1) != 1:
+        raise ValueError(f"{fn}: hist must be (B*K, cols) int64 with contiguous rows")
+    if t.dtype != torch.int64 or last_live.dtype != torch.int32:
+        raise ValueError(f"{fn}: t is an int64 word, last_live an int32 word")
+
+
 def beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_live, B, K, V, end_idx, pad_idx,
                 scores_out=None, finished_out=None):
     """per sample, the K best candidates of rule 3 (see bmhrl_beam_select in include/bmhrl_hip.h): scores (B*K) fp32 and
@@ -788,17 +804,8 @@ def beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_live, B, 
     _need_cuda(logp, scores, finished, parent, tok, hist, t, last_live)
     scores_out = scores if scores_out is None else scores_out
     finished_out = finished if finished_out is None else finished_out
-    R = B * K
-    if not (1 <= K <= BEAM_MAX and K <= V and ld >= V and logp.dtype == torch.float32 and logp.numel() >= (R - 1) * ld + V):
-        raise ValueError("beam_select: need 1 <= K <= 16, K <= V and fp32 logp rows (B*K, ld >= V)")
-    for x, dt in ((scores, torch.float32), (scores_out, torch.float32), (finished, torch.uint8), (finished_out, torch.uint8),
-                  (parent, torch.int32), (tok, torch.int64)):
-        if x.dtype != dt or x.numel() < R or not x.is_contiguous():
-            raise ValueError(f"beam_select: expected a contiguous {dt} buffer of {R} elements")
-    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != R or hist.stride(1) != 1:
-        raise ValueError("beam_select: hist must be (B*K, cols) int64 with contiguous rows")
-    if t.dtype != torch.int64 or last_live.dtype != torch.int32:
-        raise ValueError("beam_select: t is an int64 word, last_live an int32 word")
+    _check_select_buffers("beam_select", "K <= V", K, 1, V, ld, logp, scores, scores_out, finished, finished_out, parent, tok,
+                          hist, t, last_live, B * K)
     _lib.check(_lib.load().bmhrl_beam_select(logp.data_ptr(), ld, scores.data_ptr(), finished.data_ptr(), scores_out.data_ptr(),
                                              finished_out.data_ptr(), parent.data_ptr(), tok.data_ptr(), hist.data_ptr(),
                                              hist.stride(0), hist.shape[1], t.data_ptr(), last_live.data_ptr(), B, K, V, end_idx,
@@ -807,27 +814,18 @@ def beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_live, B, 
 
 def group_beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_live, B, K, V, end_idx, pad_idx, G,
                       diversity_penalty, scores_out=None, finished_out=None):
-    """beam_select for diverse beam search (csrc/group_beam.hip; rules G2-G4 of decode.py, see bmhrl_group_beam_select in
-    include/bmhrl_hip.h): the K beams of a sample form G groups of K / G that choose one after another, a later group paying
-    diversity_penalty per earlier beam that chose the token.  Buffers and outputs as beam_select's."""
+    """beam_select for diverse beam search (the grouped instantiation of csrc/beam.hip's select kernel; rules G2-G4 of
+    decode.py, see bmhrl_group_beam_select in include/bmhrl_hip.h): the K beams of a sample form G groups of K / G that choose
+    one after another, a later group paying diversity_penalty per earlier beam that chose the token.  Buffers and outputs as
+    beam_select's."""
     _need_cuda(logp, scores, finished, parent, tok, hist, t, last_live)
     scores_out = scores if scores_out is None else scores_out
     finished_out = finished if finished_out is None else finished_out
-    R = B * K
     lam = float(diversity_penalty)
-    if not (1 <= K <= BEAM_MAX and G >= 1 and K % G == 0 and K // G <= V and ld >= V and logp.dtype == torch.float32
-            and logp.numel() >= (R - 1) * ld + V):
-        raise ValueError("group_beam_select: need 1 <= K <= 16, G >= 1 dividing K, K / G <= V and fp32 logp rows (B*K, ld >= V)")
+    _check_select_buffers("group_beam_select", "G >= 1 dividing K, K / G <= V", K, G, V, ld, logp, scores, scores_out, finished,
+                          finished_out, parent, tok, hist, t, last_live, B * K)
     if not (lam >= 0 and lam < float("inf")):
         raise ValueError(f"group_beam_select: diversity_penalty must be finite and >= 0, got {diversity_penalty}")
-    for x, dt in ((scores, torch.float32), (scores_out, torch.float32), (finished, torch.uint8), (finished_out, torch.uint8),
-                  (parent, torch.int32), (tok, torch.int64)):
-        if x.dtype != dt or x.numel() < R or not x.is_contiguous():
-            raise ValueError(f"group_beam_select: expected a contiguous {dt} buffer of {R} elements")
-    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != R or hist.stride(1) != 1:
-        raise ValueError("group_beam_select: hist must be (B*K, cols) int64 with contiguous rows")
-    if t.dtype != torch.int64 or last_live.dtype != torch.int32:
-        raise ValueError("group_beam_select: t is an int64 word, last_live an int32 word")
     _lib.check(_lib.load().bmhrl_group_beam_select(
         logp.data_ptr(), ld, scores.data_ptr(), finished.data_ptr(), scores_out.data_ptr(), finished_out.data_ptr(),
         parent.data_ptr(), tok.data_ptr(), hist.data_ptr(), hist.stride(0), hist.shape[1], t.data_ptr(), last_live.data_ptr(),

@@ -1,4 +1,4 @@
-"""Beam-search decoding on the GPU: the two HIP kernels of csrc/beam.hip against torch restatements, and BeamDecoder (the
+"""Beam-search decoding on the GPU: the plain select and the reorder kernel of csrc/beam.hip against torch restatements, and BeamDecoder (the
 incremental token step on B*K rows plus the beam step, one HIP graph per token) against the greedy decoder, the
 teacher-forced full forward and the re-run path of bmhrl_amd.decode.beam_decode."""
 import time

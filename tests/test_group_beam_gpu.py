@@ -1,4 +1,4 @@
-"""Diverse (group) beam search on the GPU: bmhrl_group_beam_select (csrc/group_beam.hip) against the numpy restatement of
+"""Diverse (group) beam search on the GPU: bmhrl_group_beam_select (csrc/beam.hip) against the numpy restatement of
 tests/group_beam_reference.py with equality on every output, and GroupBeamDecoder (the incremental token step on B*K rows plus
 the grouped selection, one HIP graph per token) against the restatement on its own log-probs at every step, the re-run path,
 the teacher-forced full forward, and the properties the rules promise."""
