@@ -79,6 +79,10 @@ def validation_loop(cfg, model, optimizer, scheduler, loader, epoch, best_metric
         TBoard.add_scalar('metrics/avg_precision_at_k', avg_precision, epoch)
         TBoard.add_scalar('metrics/avg_recall_at_k', avg_recall, epoch)
         TBoard.add_scalar('metrics/avg_F1_at_k', avg_f1, epoch)
+        # AR@AN and its area (cfg.proposal_evaluator_options = {..., "proposal_recall": True}; bmhrl_amd/evaluate.py)
+        for key, tag in (('AUC', 'metrics/AUC'), ('AR@AN', 'metrics/AR_at_AN')):
+            if key in anet_metrics['Average across tIoUs']:
+                TBoard.add_scalar(tag, anet_metrics['Average across tIoUs'][key], epoch)
     if scheduler is not None:
         scheduler.step(avg_f1)
     if avg_f1 > best_metric and TBoard is not None:

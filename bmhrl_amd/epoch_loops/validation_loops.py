@@ -66,7 +66,8 @@ def calculate_metrics(reference_paths, submission_path, tIoUs, max_prop_per_vid,
     """per-tIoU and averaged scores (:160-183).  evaluator None: the reference's ANETcaptions, which needs the reference's
     evaluation package (and its Java METEOR) on sys.path -- not part of this package.  evaluator "device": this package's
     bmhrl_amd.evaluate.DenseCaptionEvaluator (what its METEOR and tokenizer are: see there), with evaluator_options as its
-    keywords (device, tokenizer, stemmer, synonyms; soda=True adds SODA_c, SODA_c_Precision and SODA_c_Recall)."""
+    keywords (device, tokenizer, stemmer, synonyms; soda=True adds SODA_c, SODA_c_Precision and SODA_c_Recall;
+    proposal_recall=True adds AUC and AR@AN; tiou_backend="device" pairs and detects through the device tIoU tables)."""
     fields = ["results", "version", "external_data"]
     if evaluator is None:
         try:

@@ -22,6 +22,11 @@ that maximises the sum of tIoU x METEOR (ops.meteor_matrix scores every predicti
 ops.soda_dp runs the max-plus dynamic programme; csrc/soda.hip), its precision, recall and F1, the best file per video, the
 mean over the ground-truth videos.  Its METEOR is the function above, so the figure is comparable between runs of this
 package, not to published SODA_c.
+
+Proposal metrics on the device (tiou_backend="device", proposal_recall=True; segment_tables, detection_scores_device,
+pair_indices_device, proposal_recall): the tIoU tables of every group are evaluated in one launch
+(ops.tiou_hits, csrc/proposal_eval.hip) with the bits of `tiou` below, and detection precision / recall, the caption pairing
+and AR@AN / AUC are built from its integers.
 """
 from __future__ import annotations
 
@@ -125,6 +130,220 @@ def detection_scores(ground_truths: Sequence[dict], prediction: Dict[str, list],
     return sum(precision) / len(precision), sum(recall) / len(recall)
 
 
+# ---- proposal metrics on the device
+class SegmentTables:
+    """What the tIoU launches of one (ground truths, prediction) job read, built once on the host (segment_tables):
+    vids            the ground-truth video ids, sorted
+    pred_seg        (NP, 2) fp64 start, end of the predictions of those videos, video by video
+    pred_video      (NP,) int64 index into vids;  pred_off (V + 1) int64: video v owns rows [pred_off[v], pred_off[v + 1])
+    pred_sentences  (NP) the predictions' sentences as given
+    ref_seg         (NR, 2) fp64 of the references, video-major, file-minor, then caption order
+    ref_file        (NR,) int64 file index;  ref_off (V + 1) int64;  ref_sentences (NR) as given
+    file_groups     (G, 4) int32 [p0, P, r0, R], one row per (video, file that holds the video), video-major, file-minor;
+                    group_video / group_file (G,) int64;  group_off (V + 1) int64: video v owns groups
+                    [group_off[v], group_off[v + 1]) -- at least one
+    video_groups    (V, 4) int32: the whole videos (all files' references of the video)
+    n_files         the number of ground-truth files
+    .on(device) gives the device copies (pred_seg, ref_seg, ops.TiouGroups of file_groups, of video_groups), made at first
+    use and kept."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+        self._dev = {}
+
+    def on(self, device):
+        import torch
+        from . import ops
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.pred_seg).to(device), torch.from_numpy(self.ref_seg).to(device),
+                              ops.TiouGroups(self.file_groups, device), ops.TiouGroups(self.video_groups, device))
+        return self._dev[key]
+
+
+def proposal_score_of(pred: dict) -> float:
+    """a prediction's "proposal_score": a one-element list or tuple counts as its element, a missing key as 0.0"""
+    score = pred.get("proposal_score", 0.0)
+    if isinstance(score, (list, tuple)):
+        score = score[0]
+    return float(score)
+
+
+def by_proposal_score(preds: Sequence[dict]) -> List[int]:
+    """the positions ordered by proposal_score descending; ties keep list order"""
+    scores = [proposal_score_of(p) for p in preds]
+    return sorted(range(len(preds)), key=lambda k: -scores[k])
+
+
+def segment_tables(ground_truths: Sequence[dict], prediction: Dict[str, list], by_score: bool = False) -> SegmentTables:
+    """The segment arrays and both group tables of a job (see SegmentTables).  `prediction` is already cut to max_proposals
+    per video.  The predictions of a video keep list order, or are ordered by_proposal_score when by_score; videos that only
+    the prediction holds are left out.  Nothing here depends on a threshold: the tables serve every tIoU and metric."""
+    vids = ground_truth_video_ids(ground_truths)
+    pred_seg, pred_sent, pred_off = [], [], [0]
+    ref_seg, ref_sent, ref_file, ref_off = [], [], [], [0]
+    groups, group_video, group_file, group_off, video_groups = [], [], [], [0], []
+    for v, vid in enumerate(vids):
+        preds = prediction.get(vid, ())
+        order = by_proposal_score(preds) if by_score else range(len(preds))
+        p0, r_start = len(pred_seg), len(ref_seg)
+        for k in order:
+            pred_seg.append((float(preds[k]["timestamp"][0]), float(preds[k]["timestamp"][1])))
+            pred_sent.append(preds[k].get("sentence", ""))
+        for f, gt in enumerate(ground_truths):
+            if vid not in gt:
+                continue
+            stamps = gt[vid]["timestamps"]
+            groups.append((p0, len(preds), len(ref_seg), len(stamps)))
+            group_video.append(v)
+            group_file.append(f)
+            for idx, stamp in enumerate(stamps):
+                ref_seg.append((float(stamp[0]), float(stamp[1])))
+                ref_sent.append(gt[vid]["sentences"][idx] if "sentences" in gt[vid] else "")
+                ref_file.append(f)
+        video_groups.append((p0, len(preds), r_start, len(ref_seg) - r_start))
+        pred_off.append(len(pred_seg))
+        ref_off.append(len(ref_seg))
+        group_off.append(len(groups))
+    i64 = lambda a: np.asarray(a, dtype=np.int64)                                                         # noqa: E731
+    pred_off = i64(pred_off)
+    return SegmentTables(
+        vids=vids, pred_seg=np.asarray(pred_seg, dtype=np.float64).reshape(-1, 2),
+        pred_video=np.repeat(np.arange(len(vids), dtype=np.int64), np.diff(pred_off)), pred_off=pred_off,
+        pred_sentences=pred_sent, ref_seg=np.asarray(ref_seg, dtype=np.float64).reshape(-1, 2), ref_file=i64(ref_file),
+        ref_off=i64(ref_off), ref_sentences=ref_sent, file_groups=np.asarray(groups, dtype=np.int32).reshape(-1, 4),
+        group_video=i64(group_video), group_file=i64(group_file), group_off=i64(group_off),
+        video_groups=np.asarray(video_groups, dtype=np.int32).reshape(-1, 4), n_files=len(ground_truths))
+
+
+def _tiou_hits(pred_seg, ref_seg, groups, tious: Sequence[float], strict: bool):
+    """ops.tiou_hits for any number of thresholds (launches of at most ops.TIOU_MAX_T): the two tables on the host"""
+    import torch
+    from . import ops
+    tious = np.asarray(tious, dtype=np.float64)
+    hits, first = [], []
+    for lo in range(0, len(tious), ops.TIOU_MAX_T):
+        h, f = ops.tiou_hits(pred_seg, ref_seg, groups, torch.from_numpy(tious[lo:lo + ops.TIOU_MAX_T]).to(pred_seg.device),
+                             strict)
+        hits.append(h)
+        first.append(f)
+    return torch.cat(hits).cpu().numpy(), torch.cat(first).cpu().numpy()
+
+
+def _group_sums(flags: np.ndarray, counts: np.ndarray) -> np.ndarray:
+    """(T, G) int64: per row of flags (T, sum counts) the number of set entries in each group's run (empty runs give 0)"""
+    c = np.zeros((flags.shape[0], flags.shape[1] + 1), dtype=np.int64)
+    np.cumsum(flags, axis=1, out=c[:, 1:])
+    off = np.concatenate([[0], np.cumsum(counts)])
+    return c[:, off[1:]] - c[:, off[:-1]]
+
+
+def detection_scores_device(tables: SegmentTables, tious: Sequence[float], device="cuda") -> List[Tuple[float, float]]:
+    """[(precision, recall)] per tIoU, the values of detection_scores: one strict launch over the (video, file) groups and
+    every threshold; per group #(pred_hits > 0) / P and #(ref_first < P) / R, the best over a video's files, the mean over
+    the ground-truth videos in their order (0 precision for a video without predictions) -- that function's float
+    expressions over the launch's integers."""
+    pred_seg, ref_seg, file_groups, _ = tables.on(device)
+    hits, first = _tiou_hits(pred_seg, ref_seg, file_groups, tious, True)
+    P, R = tables.file_groups[:, 1].astype(np.int64), tables.file_groups[:, 3].astype(np.int64)
+    if (R == 0).any():
+        raise ZeroDivisionError("a ground-truth video without timestamps")      # as detection_scores on that file
+    preds_hit = _group_sums(hits > 0, P)
+    refs_hit = _group_sums(first < np.repeat(P, R)[None, :], R)
+    starts = tables.group_off[:-1]
+    out = []
+    for t in range(len(tious)):
+        p = np.where(P > 0, preds_hit[t].astype(np.float64) / np.maximum(P, 1), 0.0)
+        r = refs_hit[t].astype(np.float64) / R
+        best_p, best_r = np.maximum.reduceat(p, starts).tolist(), np.maximum.reduceat(r, starts).tolist()
+        out.append((sum(best_p) / len(best_p), sum(best_r) / len(best_r)))
+    return out
+
+
+def pair_indices_device(tables: SegmentTables, tiou_threshold: float, device="cuda") -> Tuple[np.ndarray, np.ndarray]:
+    """(pred_index, ref_index) int64 arrays of a threshold's pairs in pair_captions' order (video, prediction, file,
+    caption): rows of tables.pred_seg and of tables.ref_seg, ref_index -1 for the one pair of a prediction that reaches no
+    reference.  Two launches over the whole videos: the hit counts (ops.tiou_hits, >=), their running sum
+    (torch.cumsum), and the rows written in order (ops.tiou_pairs)."""
+    import torch
+    from . import ops
+    pred_seg, ref_seg, _, video_groups = tables.on(device)
+    NP = video_groups.sum_p
+    if NP == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    tiou_threshold = float(tiou_threshold)
+    hits, _ = ops.tiou_hits(pred_seg, ref_seg, video_groups, torch.tensor([tiou_threshold], dtype=torch.float64, device=device),
+                            False)
+    counts = hits[0].clamp(min=1).to(torch.int64)
+    pair_off = torch.zeros(NP + 1, dtype=torch.int64, device=device)
+    torch.cumsum(counts, 0, out=pair_off[1:])
+    counts_h = counts.cpu().numpy()
+    pair_ref = ops.tiou_pairs(pred_seg, ref_seg, video_groups, tiou_threshold, pair_off, int(counts_h.sum()))
+    # a video's predictions are the rows pred_off[v] .. of pred_seg, and the video groups are laid out in that order
+    return np.repeat(np.arange(NP, dtype=np.int64), counts_h), pair_ref.cpu().numpy().astype(np.int64)
+
+
+def _trapezoid(y: Sequence[float], x: Sequence[float]) -> float:
+    """the trapezoid rule, summed left to right"""
+    total = 0.0
+    for k in range(len(x) - 1):
+        total += (x[k + 1] - x[k]) * (y[k + 1] + y[k]) / 2.0
+    return total
+
+
+def proposal_recall(ground_truths: Sequence[dict], prediction: Dict[str, list], tious: Sequence[float],
+                    max_avg_nr_proposals: int = 100, points: int = 100, device="cuda") -> dict:
+    """Average recall against the average number of proposals per video (AR@AN) and the area under that curve (AUC), the
+    ActivityNet proposal metric, per tIoU: {"AUC": [T], "AR@AN": [T], "recall_curve": (T, points),
+    "proposals_per_video": (points,)}.  `prediction` is already cut to max_proposals per video.
+
+    Per ground-truth file, with V its videos and total the number of predictions over them:
+    ratio = max_avg_nr_proposals * float(V) / total, pcn_k = (k / float(points)) * ratio for k = 1 .. points.  A video's
+    predictions are ordered by proposal_score descending (by_proposal_score); at point k its first
+    nr = int(min(P_v * pcn_k, P_v)) count.  A reference is matched at (t, k) when some counted prediction has
+    tIoU >= tious[t] with it, that is when its first rank (ops.tiou_hits, one launch for all thresholds) is < nr;
+    recall[t][k] = matched / (references of the file).  A video without predictions contributes its references and no
+    match; total == 0 (or a file without references) gives a curve of zeros.  x_k = pcn_k * (float(total) / V),
+    AUC_t = 100 * trapezoid(recall[t], x) / x[-1] (summed left to right), AR@AN_t = recall[t][-1].
+
+    With several files the curves, x and both figures are the plain mean over the files: this package's convention for
+    ActivityNet Captions' two annotation files, not part of the published metric.  The figure is comparable to
+    ActivityNet's only with its ten thresholds 0.5, 0.55 .. 0.95 and ONE annotation file, and the tIoU is `tiou` of this
+    module with its + 1e-8 in the denominator, where ActivityNet's has none."""
+    T = len(tious)
+    tables = segment_tables(ground_truths, prediction, by_score=True)
+    pred_seg, ref_seg, file_groups, _ = tables.on(device)
+    _, first = _tiou_hits(pred_seg, ref_seg, file_groups, tious, False)
+    P, R = tables.file_groups[:, 1].astype(np.int64), tables.file_groups[:, 3].astype(np.int64)
+    ref_group = np.repeat(np.arange(len(P)), R)                 # the group of every slot of `first`
+    curves, xs, aucs, ars = [], [], [], []
+    for f in range(tables.n_files):
+        mine = np.nonzero(tables.group_file == f)[0]
+        V, total, n_refs = len(mine), int(P[mine].sum()), int(R[mine].sum())
+        recall = np.zeros((T, points), dtype=np.float64)
+        x = np.zeros(points, dtype=np.float64)
+        auc = [0.0] * T
+        if total > 0 and n_refs > 0:
+            ratio = max_avg_nr_proposals * float(V) / total
+            pcn = np.array([(k / float(points)) * ratio for k in range(1, points + 1)], dtype=np.float64)
+            nr = np.minimum(P[mine, None] * pcn[None, :], P[mine, None]).astype(np.int64)              # (V, points), int()
+            slots = np.nonzero(tables.group_file[ref_group] == f)[0]
+            nr_of_slot = nr[np.searchsorted(mine, ref_group[slots])]                                    # (refs, points)
+            for t in range(T):
+                matched = (first[t, slots, None] < nr_of_slot).sum(axis=0)
+                recall[t] = matched / float(n_refs)
+            x = pcn * (float(total) / V)
+            auc = [100.0 * _trapezoid(recall[t].tolist(), x.tolist()) / float(x[-1]) for t in range(T)]
+        curves.append(recall)
+        xs.append(x)
+        aucs.append(auc)
+        ars.append([float(recall[t][-1]) for t in range(T)])
+    n = float(len(curves))
+    mean = lambda parts: sum(parts[1:], parts[0]) / n                                                  # noqa: E731
+    return {"AUC": [sum(a[t] for a in aucs) / n for t in range(T)], "AR@AN": [sum(a[t] for a in ars) / n for t in range(T)],
+            "recall_curve": mean(curves), "proposals_per_video": mean(xs)}
+
+
 def _load(x):
     if isinstance(x, dict):
         return x
@@ -140,12 +359,19 @@ class DenseCaptionEvaluator:
     (None: nltk's, an ImportError naming the two keywords when nltk is missing; False: the stage is off).
     soda=True (and not only_proposals): .evaluate() also fills SODA_c, SODA_c_Precision and SODA_c_Recall, one entry per
     tIoU, and .soda_per_video (video id -> [(precision, recall, F) per tIoU]); sort_references=True orders a video's
-    references by (start, end) like its predictions instead of keeping the file's order."""
+    references by (start, end) like its predictions instead of keeping the file's order.
+    tiou_backend="device": evaluate_detection and tokenized_pairs read the tIoU tables of one device launch
+    (segment_tables, detection_scores_device, pair_indices_device) instead of walking the interval
+    pairs in Python; the values are the same.  "host" (default) runs the Python loops.
+    proposal_recall=True: .evaluate() also fills AUC and AR@AN, one entry per tIoU, .recall_curve (T, points) and
+    .proposals_per_video (points,): proposal_recall below with its defaults, which see for the definition.  The mean of AUC
+    over the tIoUs is comparable to ActivityNet's proposal figure only with its ten thresholds 0.5 .. 0.95 and one
+    annotation file; the tIoU is `tiou` with its + 1e-8."""
 
     def __init__(self, ground_truth_filenames=None, prediction_filename=None, tious=None, max_proposals=1000,
                  prediction_fields=PREDICTION_FIELDS, verbose=False, only_proposals=False, *, device="cuda",
                  tokenizer: Callable[[str], List[str]] = tokenize, stemmer=None, synonyms=None, soda=False,
-                 sort_references=False):
+                 sort_references=False, tiou_backend="host", proposal_recall=False):
         if tious is None or len(tious) == 0:
             raise IOError("Please input a valid tIoU.")
         if not ground_truth_filenames:
@@ -162,6 +388,11 @@ class DenseCaptionEvaluator:
         self._stemmer, self._synonyms = stemmer, synonyms
         self.soda, self.sort_references = bool(soda), bool(sort_references)
         self.soda_per_video: Dict[str, List[Tuple[float, float, float]]] = {}
+        if tiou_backend not in ("host", "device"):
+            raise ValueError(f"unknown tiou_backend {tiou_backend!r} ('host' or 'device')")
+        self.tiou_backend, self.proposal_recall = tiou_backend, bool(proposal_recall)
+        self.recall_curve = self.proposals_per_video = None
+        self._tables = self._detection = self._table_tokens = None
         self.ground_truths = self.import_ground_truths(ground_truth_filenames)
         self.prediction = self.import_prediction(prediction_filename)
         self._tokens: Dict[str, Tuple[str, ...]] = {}
@@ -216,9 +447,27 @@ class DenseCaptionEvaluator:
                 precision, recall = self.evaluate_detection(t)
                 self.scores["Recall"].append(recall)
                 self.scores["Precision"].append(precision)
+        if self.proposal_recall:
+            out = proposal_recall(self.ground_truths, self.prediction, self.tious, device=self.device)
+            self.scores["AUC"], self.scores["AR@AN"] = out["AUC"], out["AR@AN"]
+            self.recall_curve, self.proposals_per_video = out["recall_curve"], out["proposals_per_video"]
+
+    def segment_tables(self) -> SegmentTables:
+        """the job's segment_tables, built at first use (the device routes share them across thresholds and metrics)"""
+        if self._tables is None:
+            self._tables = segment_tables(self.ground_truths, self.prediction)
+        return self._tables
 
     def evaluate_detection(self, tiou_threshold) -> Tuple[float, float]:
-        return detection_scores(self.ground_truths, self.prediction, tiou_threshold)
+        if self.tiou_backend == "host":
+            return detection_scores(self.ground_truths, self.prediction, tiou_threshold)
+        if self._detection is None:            # one launch for all of the evaluator's thresholds
+            tious = [float(t) for t in self.tious]
+            self._detection = dict(zip(tious, detection_scores_device(self.segment_tables(), tious, self.device)))
+        key = float(tiou_threshold)
+        if key not in self._detection:
+            self._detection[key] = detection_scores_device(self.segment_tables(), [key], self.device)[0]
+        return self._detection[key]
 
     def _tok(self, sentence: str) -> Tuple[str, ...]:
         t = self._tokens.get(sentence)
@@ -229,6 +478,8 @@ class DenseCaptionEvaluator:
     def tokenized_pairs(self, tiou_threshold):
         """(video ids, group_off, hypothesis token tuples, reference token tuples) of a threshold's pairs; the groups are
         the ground-truth videos in sorted order, those without a pair included (empty)"""
+        if self.tiou_backend == "device":
+            return self._tokenized_pairs_device(tiou_threshold)
         paired = pair_captions(self.ground_truths, self.prediction, tiou_threshold)
         vids = list(paired)
         off = [0]
@@ -239,6 +490,19 @@ class DenseCaptionEvaluator:
                 refs.append((GARBAGE,) if ref is None else self._tok(ref))
             off.append(len(hyps))
         return vids, off, hyps, refs
+
+    def _tokenized_pairs_device(self, tiou_threshold):
+        tables = self.segment_tables()
+        if self._table_tokens is None:         # every sentence of the tables, tokenized once
+            self._table_tokens = ([self._tok(remove_nonascii(s)) for s in tables.pred_sentences],
+                                  [self._tok(remove_nonascii(s)) for s in tables.ref_sentences])
+        hyp_tok, ref_tok = self._table_tokens
+        pred_index, ref_index = pair_indices_device(tables, tiou_threshold, self.device)
+        per_video = np.bincount(tables.pred_video[pred_index], minlength=len(tables.vids))
+        off = [0] + np.cumsum(per_video).tolist()
+        hyps = [hyp_tok[i] for i in pred_index.tolist()]
+        refs = [(GARBAGE,) if r < 0 else ref_tok[r] for r in ref_index.tolist()]
+        return list(tables.vids), off, hyps, refs
 
     def evaluate_tiou(self, tiou_threshold) -> Dict[str, float]:
         vids, off, hyps, refs = self.tokenized_pairs(tiou_threshold)

@@ -7,6 +7,7 @@ import math
 import os
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1040,6 +1041,96 @@ def soda_dp(pred_seg, ref_seg, hyp_off, ref_off, cell_off, S, tious):
                                          hyp_off.data_ptr(), ref_off.data_ptr(), cell_off.data_ptr(), G, S.data_ptr(), S.numel(),
                                          tious.data_ptr(), T, out.data_ptr(), stream()), "bmhrl_soda_dp")
     return out
+
+
+# ---- proposal metrics: tIoU hit counts, first ranks and the ordered pair list (csrc/proposal_eval.hip)
+TIOU_MAX_T = 16                              # BMHRL_TIOU_MAX_T of include/bmhrl_hip.h
+
+
+class TiouGroups:
+    """The group table of tiou_hits / tiou_pairs (see include/bmhrl_hip.h): `groups` (G, 4) integers, a row [p0, P, r0, R]
+    naming the predictions [p0, p0 + P) and the references [r0, r0 + R) of a group.  Keeps the three copies the ABI takes:
+    .host (G, 4) int32 numpy, .groups the same on `device`, .out_off (2, G + 1) int64 on `device` (the running sums of P and
+    of R: where a group's outputs start), and .sum_p / .sum_r.  Build it once and reuse it across launches."""
+
+    def __init__(self, groups, device):
+        g = np.asarray(groups)
+        if g.size == 0:
+            g = np.zeros((0, 4), dtype=np.int32)
+        if g.ndim != 2 or g.shape[1] != 4 or g.dtype.kind not in "iu":
+            raise ValueError("TiouGroups: groups (G, 4) integers [p0, P, r0, R] expected")
+        if g.size and (g.min() < 0 or g.max() > np.iinfo(np.int32).max):
+            raise ValueError("TiouGroups: entries must lie in [0, 2^31)")
+        self.host = np.ascontiguousarray(g, dtype=np.int32)
+        self.G = int(g.shape[0])
+        off = np.zeros((2, self.G + 1), dtype=np.int64)
+        np.cumsum(self.host[:, 1], out=off[0, 1:])
+        np.cumsum(self.host[:, 3], out=off[1, 1:])
+        self.sum_p, self.sum_r = int(off[0, -1]), int(off[1, -1])
+        self.groups = torch.from_numpy(self.host).to(device)
+        self.out_off = torch.from_numpy(off).to(device)
+
+
+def _tiou_segments(what, pred_seg, ref_seg, groups):
+    if not isinstance(groups, TiouGroups):
+        raise ValueError(f"{what}: groups must be an ops.TiouGroups")
+    for t in (pred_seg, ref_seg):
+        if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 2 or not t.is_contiguous():
+            raise ValueError(f"{what}: pred_seg / ref_seg (n, 2) fp64, contiguous, expected")
+
+
+def _tiou_out(what, t, rows, cols):
+    if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols or (t.shape[1] > 1 and t.stride(1) != 1) \
+            or (rows > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{what}: out must hold int32 ({rows}, >= {cols}) tensors with contiguous rows")
+    return t.stride(0) if rows > 1 else t.shape[1]
+
+
+def tiou_hits(pred_seg, ref_seg, groups, tious, strict, out=None):
+    """(pred_hits (T, sum P), ref_first (T, sum R)) int32 of one launch over all groups and thresholds; see bmhrl_tiou_hits
+    in include/bmhrl_hip.h.  pred_seg (n_pred, 2) / ref_seg (n_ref, 2) fp64 start, end; groups: a TiouGroups on the same
+    device; tious (T) fp64 on the device; strict: a cell passes with iou > tious[t] (True) or iou >= tious[t] (False).
+    pred_hits[t][slot] = the number of its group's references the prediction passes, ref_first[t][slot] = the smallest
+    in-group index of a prediction passing the reference, P when there is none.  out: optionally the two tensors to
+    write, rows of at least sum P / sum R words (words behind them are left alone).  Does not synchronise."""
+    _tiou_segments("tiou_hits", pred_seg, ref_seg, groups)
+    if tious.dtype != torch.float64 or tious.dim() != 1 or not tious.is_contiguous() or not 1 <= tious.numel() <= TIOU_MAX_T:
+        raise ValueError(f"tiou_hits: tious (1 <= T <= {TIOU_MAX_T}) fp64, contiguous, expected")
+    T = tious.numel()
+    if out is None:
+        out = (torch.empty(T, groups.sum_p, dtype=torch.int32, device=pred_seg.device),
+               torch.empty(T, groups.sum_r, dtype=torch.int32, device=pred_seg.device))
+    pred_hits, ref_first = out
+    ldp, ldr = _tiou_out("tiou_hits", pred_hits, T, groups.sum_p), _tiou_out("tiou_hits", ref_first, T, groups.sum_r)
+    _need_cuda(pred_seg, ref_seg, groups.groups, groups.out_off, tious, pred_hits, ref_first)
+    _lib.check(_lib.load().bmhrl_tiou_hits(pred_seg.data_ptr(), pred_seg.shape[0], ref_seg.data_ptr(), ref_seg.shape[0],
+                                           groups.host.ctypes.data, groups.groups.data_ptr(), groups.out_off.data_ptr(),
+                                           groups.G, tious.data_ptr(), T, int(bool(strict)), pred_hits.data_ptr(), ldp,
+                                           ref_first.data_ptr(), ldr, stream()), "bmhrl_tiou_hits")
+    return pred_hits[:, :groups.sum_p], ref_first[:, :groups.sum_r]
+
+
+def tiou_pairs(pred_seg, ref_seg, groups, tiou, pair_off, n_pairs, out=None):
+    """pair_ref (n_pairs) int32: behind pair_off[slot] the rows of ref_seg, ascending, that the slot's prediction reaches
+    with iou >= tiou within its group, or one -1; see bmhrl_tiou_pairs in include/bmhrl_hip.h.  pair_off (sum P + 1) int64
+    on the device: the exclusive running sum of max(pred_hits[t], 1) of tiou_hits(strict=False) over the same tables with
+    tious[t] == tiou; n_pairs: its last entry.  out: optionally the (>= n_pairs) int32 tensor to write.  Does not
+    synchronise."""
+    _tiou_segments("tiou_pairs", pred_seg, ref_seg, groups)
+    n_pairs = int(n_pairs)
+    if pair_off.dtype != torch.int64 or pair_off.dim() != 1 or pair_off.numel() != groups.sum_p + 1 or \
+            not pair_off.is_contiguous() or n_pairs < 0:
+        raise ValueError("tiou_pairs: pair_off (sum P + 1) int64, contiguous, and n_pairs >= 0 expected")
+    if out is None:
+        out = torch.empty(n_pairs, dtype=torch.int32, device=pred_seg.device)
+    if out.dtype != torch.int32 or out.dim() != 1 or out.numel() < n_pairs or not out.is_contiguous():
+        raise ValueError("tiou_pairs: out must be a contiguous int32 tensor of at least n_pairs words")
+    _need_cuda(pred_seg, ref_seg, groups.groups, groups.out_off, pair_off, out)
+    _lib.check(_lib.load().bmhrl_tiou_pairs(pred_seg.data_ptr(), pred_seg.shape[0], ref_seg.data_ptr(), ref_seg.shape[0],
+                                            groups.host.ctypes.data, groups.groups.data_ptr(), groups.out_off.data_ptr(),
+                                            groups.G, float(tiou), pair_off.data_ptr(), groups.sum_p, out.data_ptr(), n_pairs,
+                                            stream()), "bmhrl_tiou_pairs")
+    return out[:n_pairs]
 
 
 # ---- sampled caption decoding (csrc/sample.hip)

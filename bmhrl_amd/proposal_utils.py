@@ -192,7 +192,8 @@ class AnetPredictions:
             print(f"Number of videos with no proposals: {self.num_vid_w_no_props}")
         with contextlib.redirect_stdout(io.StringIO()):
             return calculate_metrics(self.cfg.reference_paths, self.submission_path, self.cfg.tIoUs, self.cfg.max_prop_per_vid,
-                                     verbose=True, only_proposals=True, evaluator=getattr(self.cfg, "caption_evaluator", None))
+                                     verbose=True, only_proposals=True, evaluator=getattr(self.cfg, "caption_evaluator", None),
+                                     evaluator_options=getattr(self.cfg, "proposal_evaluator_options", None))
 
 
 def anchors_from_segments(lengths, k, iters=100):

@@ -955,6 +955,45 @@ int bmhrl_crop_segments(const float* src, const int32_t* src_len, const double* 
                         const int32_t* seg_video, const double* seg_times, int32_t P, float pad_value, int32_t T_out,
                         float* out, int32_t* lengths, int32_t* lo, int32_t* status, bmhrl_stream_t stream);
 
+/* ---- proposal metrics (csrc/proposal_eval.hip) ----------------------------------------------------
+ * The tIoU of every prediction of a group against every reference of the group, left as integers: what detection
+ * precision / recall, AR@AN and the caption pairing of bmhrl_amd/evaluate.py are built from.  iou(i, j) is
+ * evaluate.tiou(prediction i, reference j): inter = max(0, min(e, e_i) - max(s, s_i)), union = min(max(e, e_i) - min(s, s_i),
+ * ((e - s) + e_i) - s_i), iou = inter / (union + 1e-8), fp64 in this order without contraction (csrc/tiou.h): that
+ * function's bits.  pred_seg (n_pred, 2) / ref_seg (n_ref, 2) fp64 start, end, device.
+ *
+ * The group table.  groups (G, 4) int32, one row per group: [p0, P, r0, R] -- the group's predictions are rows
+ * [p0, p0 + P) of pred_seg and its references rows [r0, r0 + R) of ref_seg.  Any P >= 0 and R >= 0; groups may overlap
+ * (the (video, file) groups of one video name the same predictions).  The outputs are laid out by the running sums of the
+ * groups' own counts: out_off (2, G + 1) int64, row 0 the exclusive running sum of P (group g's predictions own the slots
+ * [out_off[0][g], out_off[0][g] + P) of the prediction-side outputs, sum P slots in all), row 1 the same for R.  The table
+ * is passed twice: groups_host in host memory, which is checked here before anything is launched, and groups / out_off
+ * on the device, which the kernels read -- ordinary launches on the caller's stream, nothing is read back, no atomics,
+ * equal inputs give equal bits.  The caller keeps the copies equal (ops.tiou_groups builds all three from one array); a
+ * kernel checks its device row against the same bounds again, and a row that breaks them writes nothing.
+ *
+ * bmhrl_tiou_hits: a cell passes threshold t when iou > tious[t] (strict = 1) or iou >= tious[t] (strict = 0); tious (T)
+ *  fp64, device, 1 <= T <= BMHRL_TIOU_MAX_T.  pred_hits (T, ld_pred) int32: [t][slot of prediction i] = the number of the
+ *  group's references the prediction passes.  ref_first (T, ld_ref) int32: [t][slot of reference j] = the smallest in-group
+ *  index i of a prediction that passes the reference, P when none does (so 0 in a group without predictions).  Only the
+ *  first sum P / sum R words of each row are written; ld_pred >= sum P, ld_ref >= sum R.
+ * bmhrl_tiou_pairs: the ordered pair list of one threshold.  pair_off (n_slots + 1) int64, device, n_slots = sum P: the
+ *  exclusive running sum of max(pred_hits[slot], 1) of a strict = 0 call with the same tables and threshold.  The prediction
+ *  of slot s writes the rows r0 + j of its group's references with iou >= tiou, j ascending, to pair_ref[pair_off[s] ...]
+ *  (int32, n_pairs words), or a single -1 when there is none.  A word outside [pair_off[s], pair_off[s + 1]) or outside
+ *  pair_ref is never written, whatever pair_off holds.
+ * Refused with -22 before anything is launched: a null required pointer, T outside its range, strict other than 0 / 1,
+ *  negative counts, a group with a negative entry or running past n_pred / n_ref, ld_pred < sum P, ld_ref < sum R,
+ *  n_slots != sum P.  G = 0 returns 0 and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_TIOU_MAX_T 16
+int bmhrl_tiou_hits(const double* pred_seg, int32_t n_pred, const double* ref_seg, int32_t n_ref, const int32_t* groups_host,
+                    const int32_t* groups, const int64_t* out_off, int32_t G, const double* tious, int32_t T, int32_t strict,
+                    int32_t* pred_hits, int64_t ld_pred, int32_t* ref_first, int64_t ld_ref, bmhrl_stream_t stream);
+int bmhrl_tiou_pairs(const double* pred_seg, int32_t n_pred, const double* ref_seg, int32_t n_ref, const int32_t* groups_host,
+                     const int32_t* groups, const int64_t* out_off, int32_t G, double tiou, const int64_t* pair_off,
+                     int64_t n_slots, int32_t* pair_ref, int64_t n_pairs, bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
