@@ -96,7 +96,10 @@ struct RowTarget {
   }
 };
 
-__device__ __forceinline__ float xlogx(float d) { return d > 0.f ? d * __logf(d) : 0.f; }
+// (logf / expf, not the fast intrinsics, for everything that is computed once per row -- the amplitude, the logarithms of the
+// special columns -- and for the unreduced divergence: __expf(lp) is 4e-7 off at lp = -9 and that error reached amp_out, the pad
+// column of the divergence and d rows / d amp; tests/test_loss_paths_gpu.py holds them to 2^-22)
+__device__ __forceinline__ float xlogx(float d) { return d > 0.f ? d * logf(d) : 0.f; }
 
 // pad rows are zeroed only if the SUM of padded flat indices is positive: row r > 0 always qualifies itself; row 0
 // qualifies only if some other row is padded too.
@@ -122,7 +125,8 @@ __device__ RowTarget make_target(const float* lp, const int64_t* trg, const int6
   T.zero_row = pad_row_zeroed(trg, row, rows, pad, zero_pad_rows);
   T.amp = 0.f;
   if (btrg) {
-    const float raw = score[row] * __expf(lp[T.a]) * n_row[row];
+    // n_row == nullptr: `score` IS the amplitude, an argument and not a function of the log-probs (functional.GivenAmpKLFn)
+    const float raw = n_row ? score[row] * expf(lp[T.a]) * n_row[row] : score[row];
     if (raw_amp) *raw_amp = raw;
     T.amp = fminf(fmaxf(raw, 0.f), 1.f);
   }
@@ -188,13 +192,14 @@ __global__ void smooth_kl_bwd_kernel(const float* __restrict__ logp, long ld, co
   const float scale = loss_scale2 ? loss_scale[0] * loss_scale2[0] : loss_scale[0];
   // d rowloss / d logp_v = -dist'_v, plus the amplitude path on column a:
   //   d rowloss/d amp = keep * [ (log d'_a + 1 - logp_a) - (t != pad) * (log d'_t + 1 - logp_t) ],  d amp/d logp_a = raw
+  // (no such path when the amplitude is given, n_row == nullptr)
   float extra_a = 0.f;
-  if (T.a >= 0 && !T.zero_row && raw >= 0.f && raw <= 1.f) {
+  if (T.a >= 0 && n_row && !T.zero_row && raw >= 0.f && raw <= 1.f) {
     const float da = T.at(T.a);
-    float g = __logf(da) + 1.f - lp[T.a];
+    float g = logf(da) + 1.f - lp[T.a];
     if (T.t != T.pad) {
       const float dt = T.at(T.t);
-      g -= __logf(dt) + 1.f - lp[T.t];
+      g -= logf(dt) + 1.f - lp[T.t];
     }
     extra_a = T.keep * g * raw;
   }
@@ -205,7 +210,8 @@ __global__ void smooth_kl_bwd_kernel(const float* __restrict__ logp, long ld, co
   if (T.a >= 0 && T.a != T.t && T.a != T.pad) dsum += T.at(T.a);
   const float G = wrt_logits ? (-dsum + extra_a) : 0.f;  // sum_v d rowloss / d logp_v (log-softmax backward term)
   for (int c = threadIdx.x; c < V; c += blockDim.x) {
-    float g = -T.at(c) - (wrt_logits ? __expf(lp[c]) * G : 0.f);
+    // (expf, as in head_loss_kernel: __expf(lp) is 4e-7 off at lp = -9, which the pad column of the fp32 gradient shows)
+    float g = -T.at(c) - (wrt_logits ? expf(lp[c]) * G : 0.f);
     if (c == T.a) g += extra_a;
     g *= scale;
     if (gb) gb[row * ldg + c] = (bf16_t)g;
@@ -214,7 +220,8 @@ __global__ void smooth_kl_bwd_kernel(const float* __restrict__ logp, long ld, co
 }
 
 // d rowloss / d log(raw amplitude) of every row (0 where the clamp is active, on pad rows the reference zeroes, without a sampled
-// token): what the backward adds to column a of the row itself.  The manager branch of biased_kl() needs it per row: its
+// token): what the backward adds to column a of the row itself.  With a given amplitude (n_row == nullptr): d rowloss / d amp,
+// on the closed interval [0, 1].  The manager branch of biased_kl() needs it per row: its
 // amplitude holds the PRODUCT of the sampled tokens' probabilities over a segment, so the same quantity also flows to the
 // other tokens of the segment (epoch_loops/captioning_bmrl_loops.py:299-317).
 __global__ void smooth_kl_amp_grad_kernel(const float* __restrict__ logp, long ld, const int64_t* __restrict__ trg,
@@ -228,9 +235,9 @@ __global__ void smooth_kl_amp_grad_kernel(const float* __restrict__ logp, long l
   const RowTarget T = make_target(lp, trg, btrg, score, n_row, smoothing, pad, zero_pad_rows, row, rows, V, &raw);
   float e = 0.f;
   if (T.a >= 0 && !T.zero_row && raw >= 0.f && raw <= 1.f) {
-    float g = __logf(T.at(T.a)) + 1.f - lp[T.a];
-    if (T.t != T.pad) g -= __logf(T.at(T.t)) + 1.f - lp[T.t];
-    e = T.keep * g * raw;
+    float g = logf(T.at(T.a)) + 1.f - lp[T.a];
+    if (T.t != T.pad) g -= logf(T.at(T.t)) + 1.f - lp[T.t];
+    e = T.keep * g * (n_row ? raw : 1.f);
   }
   out[row] = e;
 }
@@ -323,7 +330,7 @@ __global__ __launch_bounds__(256) void head_loss_kernel(float* __restrict__ x, l
       bf16x4 o;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float g = -T.at(c + j) - __expf(v[i][j]) * G;
+        float g = -T.at(c + j) - expf(v[i][j]) * G;
         g *= scale;
         o[j] = (bf16_t)g;
       }
@@ -375,7 +382,6 @@ __global__ __launch_bounds__(256) void head_loss_kernel(float* __restrict__ x, l
   atomicExch(sync + 2, 0u);
 }
 
-// Inverse-CDF categorical sample with one uniform per row (or arg-max), block per row.
 // loss = weight * sum(row_loss) / n_tokens and scale = weight / n_tokens (what the backward multiplies every row by), with
 // n_tokens = #(trg != pad): the reduction epoch_loops/captioning_bmrl_loops.py:1156-1158 (warmstart) / :846-847,859 (RL, with
 // `factor` = 4/20) does with torch.sum / n_tokens.  One block; rows = B*L is a few hundred.
@@ -406,6 +412,8 @@ __global__ void token_loss_reduce_kernel(const float* __restrict__ row_loss, con
   }
 }
 
+// Inverse-CDF categorical sample with one uniform per row (or arg-max), block per row.  The token is always in [0, V): the
+// arg-max of a row without an entry above -inf is 0.
 __global__ void sample_kernel(const float* __restrict__ logp, long ld, int64_t* __restrict__ out, float* __restrict__ p_out,
                               int V, int greedy, uint64_t seed, const uint64_t* __restrict__ seed_dev, long row_offset) {
   if (seed_dev) seed += seed_dev[0];          // a device word advanced per step: fresh samples under graph replay
@@ -427,6 +435,9 @@ __global__ void sample_kernel(const float* __restrict__ logp, long ld, int64_t* 
     if (tid == 0) {
       for (int i = 1; i < nt; ++i)
         if (part[i] > bv) { bv = part[i]; bi = best_i[i]; }  // first maximum wins, like torch.argmax
+      // a row in which no entry exceeds -inf (all NaN after a diverged step, or all -inf) has no maximum: the token is 0, always
+      // in [0, V), and p_out = exp(lp[0]) still shows the NaN
+      if (bi >= V) bi = 0;
       out[row] = bi;
       if (p_out) p_out[row] = __expf(lp[bi]);
     }
@@ -509,7 +520,7 @@ extern "C" int bmhrl_smooth_kl_fwd(const float* logp, int64_t ld, const int64_t*
                                    int32_t zero_pad_rows, float* row_loss, float* amp_out, int64_t rows, int32_t V,
                                    bmhrl_stream_t stream) {
   BMHRL_CHECK_ARG(logp && trg && row_loss && rows > 0 && V > 2);
-  BMHRL_CHECK_ARG(!biased_trg || (score && n_row));
+  BMHRL_CHECK_ARG(!biased_trg || score);
   hipLaunchKernelGGL(smooth_kl_fwd_kernel, dim3((unsigned)rows), dim3(256), 0, S_(stream), logp, (long)ld, trg, biased_trg,
                      score, n_row, smoothing, pad_idx, zero_pad_rows, row_loss, amp_out, (long)rows, V);
   return hip_status(hipGetLastError());
@@ -519,7 +530,7 @@ extern "C" int bmhrl_smooth_kl_full(const float* logp, int64_t ld, const int64_t
                                     const float* n_row, float smoothing, int32_t pad_idx, int32_t zero_pad_rows, float* out,
                                     int64_t rows, int32_t V, bmhrl_stream_t stream) {
   BMHRL_CHECK_ARG(logp && trg && out && rows > 0 && V > 2);
-  BMHRL_CHECK_ARG(!biased_trg || (score && n_row));
+  BMHRL_CHECK_ARG(!biased_trg || score);
   hipLaunchKernelGGL(smooth_kl_full_kernel, dim3((unsigned)rows), dim3(256), 0, S_(stream), logp, (long)ld, trg, biased_trg, score,
                      n_row, smoothing, pad_idx, zero_pad_rows, out, (long)rows, V);
   return hip_status(hipGetLastError());
@@ -554,7 +565,7 @@ extern "C" int bmhrl_smooth_kl_bwd(const float* logp, int64_t ld, const int64_t*
                                    void* dlogits_bf16, int64_t ldg, float* dlogits_f32, int64_t rows, int32_t V,
                                    bmhrl_stream_t stream) {
   BMHRL_CHECK_ARG(logp && trg && loss_scale && (dlogits_bf16 || dlogits_f32) && rows > 0 && V > 2);
-  BMHRL_CHECK_ARG(!biased_trg || (score && n_row));
+  BMHRL_CHECK_ARG(!biased_trg || score);
   hipLaunchKernelGGL(smooth_kl_bwd_kernel, dim3((unsigned)rows), dim3(256), 0, S_(stream), logp, (long)ld, trg, biased_trg,
                      score, n_row, smoothing, pad_idx, zero_pad_rows, loss_scale, loss_scale2, wrt_logits, (bf16_t*)dlogits_bf16,
                      (long)ldg, dlogits_f32, (long)rows, V);
@@ -564,7 +575,7 @@ extern "C" int bmhrl_smooth_kl_bwd(const float* logp, int64_t ld, const int64_t*
 extern "C" int bmhrl_smooth_kl_amp_grad(const float* logp, int64_t ld, const int64_t* trg, const int64_t* biased_trg,
                                         const float* score, const float* n_row, float smoothing, int32_t pad_idx,
                                         int32_t zero_pad_rows, float* out, int64_t rows, int32_t V, bmhrl_stream_t stream) {
-  BMHRL_CHECK_ARG(logp && trg && biased_trg && score && n_row && out && rows > 0 && V > 2);
+  BMHRL_CHECK_ARG(logp && trg && biased_trg && score && out && rows > 0 && V > 2);
   hipLaunchKernelGGL(smooth_kl_amp_grad_kernel, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, S_(stream), logp, (long)ld,
                      trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, out, (long)rows, V);
   return hip_status(hipGetLastError());

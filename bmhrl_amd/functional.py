@@ -1958,10 +1958,9 @@ class GivenAmpKLFn(torch.autograd.Function):
     ordinary tensor ARGUMENT.  Whether the divergence's gradient reaches the prediction through it is autograd's business -- an
     amplitude computed from the prediction (the loops' clamp(score * p(a) * n, 0, 1)) carries it, a detached one does not --, so
     this node differentiates w.r.t. both inputs: d rows / d log-probs with the amplitude held fixed, and d rows / d amplitude.
-    Same kernels as SmoothKLFn (which forms the amplitude itself and therefore always includes the path through p(a)): the
-    given amplitude is reproduced as score' * p(a) with score' = amp / p(a); bmhrl_smooth_kl_amp_grad gives the share e of the
-    gradient that SmoothKLFn's backward sends through the row's own token, which is taken out of d log-probs again and,
-    divided by the amplitude, is d rows / d amp.  Amplitudes are expected in [0, 1] (every caller clamps them)."""
+    Same kernels as SmoothKLFn in their given-amplitude form (amp_given, n_row = None: `score` is the amplitude itself, the gradient
+    kernel has no path through it, and bmhrl_smooth_kl_amp_grad returns d rows / d amp, exact at amplitudes 0 and 1 too).
+    Amplitudes are expected in [0, 1] (every caller clamps them); the kernels clamp them all the same."""
 
     @staticmethod
     def forward(ctx, logp, trg, biased_trg, amp, smoothing, pad_idx):
@@ -1972,38 +1971,29 @@ class GivenAmpKLFn(torch.autograd.Function):
         trg = trg.contiguous().view(-1)
         bt = biased_trg.contiguous().view(-1)
         a = amp.detach().float().contiguous().view(-1)
-        p = torch.gather(logp.view(rows, V), 1, bt.view(rows, 1)).squeeze(1).exp().clamp_min(1e-30)
-        one = torch.ones_like(a)
         row_loss = torch.empty(rows, device=dev)
-        ops.smooth_kl_fwd(logp, V, trg, bt, (a / p).contiguous(), one, smoothing, pad_idx, -1, row_loss, None, rows, V)
-        ctx.save_for_backward(logp, trg, bt, a, p)
+        ops.smooth_kl_fwd(logp, V, trg, bt, a, None, smoothing, pad_idx, -1, row_loss, None, rows, V, amp_given=True)
+        ctx.save_for_backward(logp, trg, bt, a)
         ctx.cfg = (B, S, V, smoothing, pad_idx, tuple(amp.shape))
         return row_loss
 
     @staticmethod
     def backward(ctx, drow):
         B, S, V, smoothing, pad_idx, amp_shape = ctx.cfg
-        logp, trg, bt, a, p = ctx.saved_tensors
+        logp, trg, bt, a = ctx.saved_tensors
         rows = B * S
         dev = logp.device
-        one = torch.ones(rows, device=dev)
         drow = drow.contiguous().view(rows)
         g_logp = g_amp = None
-        sc = (a / p).contiguous()
         if ctx.needs_input_grad[0]:
             g = torch.empty(rows, V, device=dev)
-            ops.smooth_kl_bwd(logp, V, trg, bt, sc, one, smoothing, pad_idx, -1, one[:1], None, 0, g, rows, V, wrt_logits=False)
-            e = torch.empty(rows, device=dev)
-            ops.smooth_kl_amp_grad(logp, V, trg, bt, sc, one, smoothing, pad_idx, -1, e, rows, V)
-            g.scatter_add_(1, bt.view(rows, 1), (-e).view(rows, 1))        # the amplitude is an input here, not a function of p(a)
+            ops.smooth_kl_bwd(logp, V, trg, bt, a, None, smoothing, pad_idx, -1, torch.ones(1, device=dev), None, 0, g, rows, V,
+                              wrt_logits=False, amp_given=True)
             g_logp = (g * drow.view(rows, 1)).view(B, S, V)
         if ctx.needs_input_grad[3]:
-            # d rows / d amp = e / amp; evaluated at >= 1e-6 so that an amplitude of exactly 0 has its (finite) slope
-            # (and at most 1 - 1e-6: (amp / p) * p may round to just above 1, which the kernel reads as a clamped amplitude)
-            ac = a.clamp(1e-6, 1.0 - 1e-6)
             e = torch.empty(rows, device=dev)
-            ops.smooth_kl_amp_grad(logp, V, trg, bt, (ac / p).contiguous(), one, smoothing, pad_idx, -1, e, rows, V)
-            g_amp = (e / ac * drow).view(amp_shape)
+            ops.smooth_kl_amp_grad(logp, V, trg, bt, a, None, smoothing, pad_idx, -1, e, rows, V, amp_given=True)
+            g_amp = (e * drow).view(amp_shape)
         return g_logp, None, None, g_amp, None, None
 
 

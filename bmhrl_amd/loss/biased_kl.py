@@ -38,11 +38,10 @@ class BiasedKL(nn.Module):
         """the (B*S, V) tensor the reference's forward returns (loss/biased_kl.py:52) for a GIVEN amplitude; no gradient."""
         B, S, V = pred.shape
         with torch.no_grad():
-            p = torch.gather(torch.exp(pred), 2, biased_trg.unsqueeze(-1)).squeeze(-1)
-            score = (biased_offset.detach().float() / p.clamp_min(1e-30)).contiguous().view(-1)
+            amp = biased_offset.detach().float().contiguous().view(-1)
             out = torch.empty(B * S, V, device=pred.device)
-            ops.smooth_kl_full(pred.detach().contiguous(), V, trg.contiguous().view(-1), biased_trg.contiguous().view(-1), score,
-                               torch.ones_like(score), float(self.ls), int(self.pad_idx), -1, out, B * S, V)
+            ops.smooth_kl_full(pred.detach().contiguous(), V, trg.contiguous().view(-1), biased_trg.contiguous().view(-1), amp,
+                               None, float(self.ls), int(self.pad_idx), -1, out, B * S, V, amp_given=True)
         return out
 
     def forward(self, pred, trg, biased_trg, biased_offset, segments=None):

@@ -512,30 +512,44 @@ def log_softmax_(logits, ld, rows, V):
     _lib.check(_lib.load().bmhrl_log_softmax(logits.data_ptr(), ld, rows, V, stream()), "bmhrl_log_softmax")
 
 
-def smooth_kl_fwd(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, row_loss, amp_out, rows, V):
+def _amp_form(what, biased_trg, n_row, amp_given):
+    """the C entry points read a biased call without n_row as "score IS the amplitude"; here that form has to be asked for by
+    name, so that a caller who merely forgot n_row gets an error and not another loss"""
+    if biased_trg is not None and (n_row is None) != bool(amp_given):
+        raise ValueError(f"{what}: n_row is required with biased_trg unless amp_given=True (score is then the amplitude itself "
+                         "and n_row must be None)")
+
+
+def smooth_kl_fwd(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, row_loss, amp_out, rows, V,
+                  amp_given=False):
+    _amp_form("smooth_kl_fwd", biased_trg, n_row, amp_given)
     _lib.check(_lib.load().bmhrl_smooth_kl_fwd(logp.data_ptr(), ld, trg.data_ptr(), _p(biased_trg), _p(score), _p(n_row),
                                                smoothing, pad_idx, zero_pad_rows, row_loss.data_ptr(), _p(amp_out), rows, V,
                                                stream()), "bmhrl_smooth_kl_fwd")
 
 
-def smooth_kl_full(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, out, rows, V):
+def smooth_kl_full(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, out, rows, V, amp_given=False):
     """the unreduced (rows, V) divergence of LabelSmoothing / BiasedKL (no gradient: the differentiable form is the row sums)"""
+    _amp_form("smooth_kl_full", biased_trg, n_row, amp_given)
     _need_cuda(logp, out)
     _lib.check(_lib.load().bmhrl_smooth_kl_full(logp.data_ptr(), ld, trg.data_ptr(), _p(biased_trg), _p(score), _p(n_row), smoothing,
                                                 pad_idx, zero_pad_rows, out.data_ptr(), rows, V, stream()), "bmhrl_smooth_kl_full")
 
 
 def smooth_kl_bwd(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, loss_scale, g_bf16, ldg,
-                  g_f32, rows, V, wrt_logits=True, loss_scale2=None):
+                  g_f32, rows, V, wrt_logits=True, loss_scale2=None, amp_given=False):
     """loss_scale (and the optional loss_scale2, multiplied in) are one-element device tensors"""
+    _amp_form("smooth_kl_bwd", biased_trg, n_row, amp_given)
     _lib.check(_lib.load().bmhrl_smooth_kl_bwd(logp.data_ptr(), ld, trg.data_ptr(), _p(biased_trg), _p(score), _p(n_row),
                                                smoothing, pad_idx, zero_pad_rows, loss_scale.data_ptr(), _p(loss_scale2),
                                                int(wrt_logits), _p(g_bf16), ldg, _p(g_f32), rows, V, stream()), "bmhrl_smooth_kl_bwd")
 
 
-def smooth_kl_amp_grad(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, out, rows, V):
+def smooth_kl_amp_grad(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, out, rows, V, amp_given=False):
+    """d rows / d log(raw amplitude); amp_given (n_row None): `score` is the amplitude itself and the result is d rows / d amplitude"""
+    _amp_form("smooth_kl_amp_grad", biased_trg, n_row, amp_given)
     _lib.check(_lib.load().bmhrl_smooth_kl_amp_grad(logp.data_ptr(), ld, trg.data_ptr(), biased_trg.data_ptr(), score.data_ptr(),
-                                                    n_row.data_ptr(), smoothing, pad_idx, zero_pad_rows, out.data_ptr(), rows, V,
+                                                    _p(n_row), smoothing, pad_idx, zero_pad_rows, out.data_ptr(), rows, V,
                                                     stream()), "bmhrl_smooth_kl_amp_grad")
 
 
@@ -565,6 +579,9 @@ def log_softmax_bwd(dlogp, logp, ld, g_bf16, ldg, rows, V):
 
 
 def sample_tokens(logp, ld, out, p_out, rows, V, greedy, seed, seed_dev=None, row_offset=0):
+    """one token per row, inverse-CDF sample for uniform01(seed + seed_dev[0], row + row_offset) or (greedy) the first maximum;
+    p_out = exp(logp[token]).  The token is always in [0, V): a row in which no entry exceeds -inf (all NaN, all -inf) gives
+    token 0 under greedy, and its p_out = exp(logp[row, 0]) still shows the NaN."""
     _lib.check(_lib.load().bmhrl_sample_tokens(logp.data_ptr(), ld, out.data_ptr(), _p(p_out), rows, V, int(greedy), seed,
                                                _p(seed_dev), row_offset, stream()), "bmhrl_sample_tokens")
 

@@ -404,6 +404,8 @@ int bmhrl_scatter_add_rows(const float* dout, const int32_t* src, float* dx, int
  *                       (wrt_logits = 0) -> bf16 (rows, ldg) and/or fp32 (rows, V), incl. the path through amp.
  *  bmhrl_log_softmax_bwd: dlogits = dlogp - exp(logp) * rowsum(dlogp) -> bf16 (rows, ldg)
  *  zero_pad_rows: the reference's `idx.sum() > 0` guard: 1/0 forces it, -1 lets the kernel evaluate it on the device.
+ *  n_row == NULL with biased_trg given: `score` IS the amplitude, an argument of BiasedKL.forward and not a function of the
+ *                       log-probs (clamped to [0, 1] all the same): bmhrl_smooth_kl_bwd then has no path through it.
  * ------------------------------------------------------------------------------------------- */
 int bmhrl_log_softmax(float* logits, int64_t ld, int64_t rows, int32_t V, bmhrl_stream_t stream);
 int bmhrl_smooth_kl_fwd(const float* logp, int64_t ld, const int64_t* trg, const int64_t* biased_trg,
@@ -440,7 +442,8 @@ int bmhrl_log_softmax_bwd(const float* dlogp, const float* logp, int64_t ld, voi
                           int64_t rows, int32_t V, bmhrl_stream_t stream);
 /* out[row] = d rowloss / d log(raw amplitude) (0 where clamp(., 0, 1) is active): the share of the gradient that reaches the
  * row through its amplitude.  Manager branch of biased_kl(), epoch_loops/captioning_bmrl_loops.py:299-317: the amplitude holds
- * the product of p(a) over a segment, so this also flows to the segment's other tokens (bmhrl_amd/functional.py ManagerKLFn). */
+ * the product of p(a) over a segment, so this also flows to the segment's other tokens (bmhrl_amd/functional.py ManagerKLFn).
+ * With a given amplitude (n_row == NULL): out[row] = d rowloss / d amplitude, on the closed interval [0, 1] (GivenAmpKLFn). */
 int bmhrl_smooth_kl_amp_grad(const float* logp, int64_t ld, const int64_t* trg, const int64_t* biased_trg, const float* score,
                              const float* n_row, float smoothing, int32_t pad_idx, int32_t zero_pad_rows, float* out,
                              int64_t rows, int32_t V, bmhrl_stream_t stream);
