@@ -160,6 +160,9 @@ PROTOTYPES = {
     "bmhrl_tiou_hits": [ptr, i32, ptr, i32, ptr, ptr, ptr, i32, ptr, i32, i32, ptr, i64, ptr, i64, ptr],
     "bmhrl_tiou_pairs": [ptr, i32, ptr, i32, ptr, ptr, ptr, i32, f64, ptr, i64, ptr, i64, ptr],
     "bmhrl_crop_segments": [ptr, ptr, ptr, i32, i32, i32, ptr, ptr, i32, f32, i32, ptr, ptr, ptr, ptr, ptr],
+    "bmhrl_rollout_advantage": [ptr, i64, i32, i32, i32, i64, ptr, i64, i32, ptr, ptr, ptr, ptr, ptr, i64, ptr, ptr],
+    "bmhrl_policy_loss_fwd": [ptr, i64, ptr, ptr, ptr, f32, ptr, ptr, ptr, i64, i32, ptr],
+    "bmhrl_policy_loss_bwd": [ptr, i64, ptr, ptr, ptr, f32, ptr, ptr, ptr, ptr, i64, i64, i32, ptr],
 }
 
 _lib = None

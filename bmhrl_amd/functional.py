@@ -2328,3 +2328,47 @@ class ProposalLossFn(torch.autograd.Function):
         dx, = ctx.saved_tensors
         g = dx * dtotal
         return (g if ctx.in_dtype == torch.float32 else g.to(ctx.in_dtype),) + (None,) * 11
+
+
+class PolicyLossFn(torch.autograd.Function):
+    """The self-critical policy loss on the log-probs of the training forward (csrc/policy_loss.hip):
+    per (rollout, step) row the policy term -w logp[a] -- or, with clip > 0 and the rollout's log-probs logq, the clipped-ratio
+    form -min(rho w, clamp(rho, 1 - clip, 1 + clip) w), rho = exp(logp[a] - logq) -- and, with ent_weight, -beta H of the row.
+    logp (R, m, V) fp32; action (R, m) int64; weight (R, m) fp32 (advantage / token count, 0 behind a rollout's end); logq
+    (R, m) fp32 or None; ent_weight (R, m) fp32 or None.  Returns (row_loss (R*m,), row_entropy (R*m,)); row_entropy is not
+    differentiable, and only logp is differentiated (the log-probs are independent variables, as in SmoothKLFn: the worker
+    head's log-softmax backward does the rest).  The backward writes the dense (R, m, V) gradient in one launch."""
+
+    @staticmethod
+    def forward(ctx, logp, action, weight, logq, clip, ent_weight):
+        R, m, V = logp.shape
+        rows = R * m
+        dev = logp.device
+        clip = float(clip)
+        if (clip > 0) != (logq is not None):
+            raise ValueError("PolicyLossFn: clip > 0 and logq go together")
+        logp = logp.contiguous()
+        flat = lambda t, dt: None if t is None else t.detach().reshape(-1).to(dt).contiguous()     # noqa: E731
+        a, w, lq, be = flat(action, torch.int64), flat(weight, torch.float32), flat(logq, torch.float32), \
+            flat(ent_weight, torch.float32)
+        if a.numel() != rows or w.numel() != rows or (lq is not None and lq.numel() != rows) or \
+                (be is not None and be.numel() != rows):
+            raise ValueError(f"PolicyLossFn: action / weight / logq / ent_weight must hold {rows} entries")
+        row_loss = torch.empty(rows, device=dev)
+        row_entropy = torch.empty(rows, device=dev)
+        ops.policy_loss_fwd(logp, V, a, w, lq, clip, be, row_loss, row_entropy, rows, V)
+        ctx.save_for_backward(logp, a, w, lq, be)
+        ctx.cfg = (R, m, V, clip)
+        ctx.mark_non_differentiable(row_entropy)
+        return row_loss, row_entropy
+
+    @staticmethod
+    def backward(ctx, drow, _dentropy):
+        R, m, V, clip = ctx.cfg
+        logp, a, w, lq, be = ctx.saved_tensors
+        rows = R * m
+        dev = logp.device
+        g = torch.empty(R, m, V, device=dev)
+        ops.policy_loss_bwd(logp, V, a, w, lq, clip, be, torch.ones(1, device=dev), drow.contiguous().view(rows).float(), g, V,
+                            rows, V)
+        return g, None, None, None, None, None

@@ -1487,3 +1487,66 @@ def crop_segments(src, src_len, durations, seg_video, seg_times, pad_value, T_ou
                                                out.data_ptr(), lengths.data_ptr(), lo.data_ptr(), status.data_ptr(), stream()),
                "bmhrl_crop_segments")
     return out, lengths, lo, status
+
+
+# ---- self-critical policy gradient on sampled rollouts (csrc/policy_loss.hip)
+ROLLOUT_MAX_N = 16                            # BMHRL_ROLLOUT_MAX_N of include/bmhrl_hip.h
+BASELINE_NONE, BASELINE_LEAVE_ONE_OUT, BASELINE_GIVEN = 0, 1, 2      # BMHRL_BASELINE_*
+
+
+def _rows2d(t, dtype, rows, cols, what):
+    """row stride of a (rows, >= cols) tensor of `dtype` with unit column stride"""
+    if t.dtype != dtype or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what}: expected a ({rows}, >= {cols}) {dtype} tensor with contiguous rows")
+    return t.stride(0) if rows > 1 else max(t.stride(0), cols)
+
+
+def rollout_advantage(toks, n, m, end_idx, scores, baseline=BASELINE_LEAVE_ONE_OUT, base=None, out=None):
+    """rules R1-R7 of bmhrl_rollout_advantage (include/bmhrl_hip.h): toks (B * n, >= m + 1) int64 sample-major, column 0 the
+    start token; scores (B * n, >= m) fp64, the per-prefix table of toks[:, 1:]; base (B,) fp64 with BASELINE_GIVEN.
+    -> (len (B * n,) int32, reward (B * n,) fp64, adv (B * n,) fp64, weight (B * n, m) fp32, stats (4,) fp64 = mean reward,
+    mean baseline, mean length, token count).  out: the same five tensors to write into (weight may be a view with a wider
+    row stride).  Nothing is read on the host."""
+    _need_cuda(toks, scores, base)
+    n, m, baseline = int(n), int(m), int(baseline)
+    if not (1 <= n <= ROLLOUT_MAX_N and 1 <= m <= REWARDS_MAX_L):
+        raise ValueError(f"rollout_advantage: need 1 <= n <= {ROLLOUT_MAX_N} and 1 <= m <= {REWARDS_MAX_L}")
+    rows = toks.shape[0] if toks.dim() == 2 else 0
+    if rows < 1 or rows % n:
+        raise ValueError("rollout_advantage: toks must hold n consecutive rows per clip")
+    B = rows // n
+    ldt = _rows2d(toks, torch.int64, rows, m + 1, "rollout_advantage: toks")
+    lds = _rows2d(scores, torch.float64, rows, m, "rollout_advantage: scores")
+    if baseline == BASELINE_GIVEN and (base is None or base.dtype != torch.float64 or base.numel() != B or not base.is_contiguous()):
+        raise ValueError(f"rollout_advantage: BASELINE_GIVEN needs a contiguous ({B},) fp64 base")
+    dev = toks.device
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.float64, device=dev),
+               torch.empty(rows, dtype=torch.float64, device=dev), torch.empty(rows, m, device=dev),
+               torch.empty(4, dtype=torch.float64, device=dev))
+    ln, reward, adv, weight, stats = out
+    ldw = _rows2d(weight, torch.float32, rows, m, "rollout_advantage: weight")
+    for t, dt, k in ((ln, torch.int32, rows), (reward, torch.float64, rows), (adv, torch.float64, rows), (stats, torch.float64, 4)):
+        if t.dtype != dt or t.numel() != k or not t.is_contiguous() or t.device != dev:
+            raise ValueError("rollout_advantage: len / reward / adv / stats must be contiguous int32 / fp64 tensors on toks' device")
+    _lib.check(_lib.load().bmhrl_rollout_advantage(toks.data_ptr(), ldt, B, n, m, int(end_idx), scores.data_ptr(), lds, baseline,
+                                                   _p(base), ln.data_ptr(), reward.data_ptr(), adv.data_ptr(), weight.data_ptr(),
+                                                   ldw, stats.data_ptr(), stream()), "bmhrl_rollout_advantage")
+    return ln, reward, adv, weight[:, :m], stats
+
+
+def policy_loss_fwd(logp, ld, action, weight, logq, clip, ent_weight, row_loss, row_entropy, rows, V):
+    """row_loss / row_entropy (rows,) fp32 of bmhrl_policy_loss_fwd: logp (rows, V) fp32 with row stride ld, action (rows,)
+    int64, weight (rows,) fp32, logq (rows,) fp32 with clip > 0 (both or neither), ent_weight (rows,) fp32 or None"""
+    _need_cuda(logp, action, weight, logq, ent_weight, row_loss, row_entropy)
+    _lib.check(_lib.load().bmhrl_policy_loss_fwd(logp.data_ptr(), ld, action.data_ptr(), weight.data_ptr(), _p(logq), float(clip),
+                                                 _p(ent_weight), row_loss.data_ptr(), row_entropy.data_ptr(), rows, V, stream()),
+               "bmhrl_policy_loss_fwd")
+
+
+def policy_loss_bwd(logp, ld, action, weight, logq, clip, ent_weight, gscale, drow, dlogp, ldg, rows, V):
+    """the dense gradient dlogp (rows, V) fp32 with row stride ldg of bmhrl_policy_loss_bwd, times gscale[0] * drow[row]"""
+    _need_cuda(logp, action, weight, logq, ent_weight, gscale, drow, dlogp)
+    _lib.check(_lib.load().bmhrl_policy_loss_bwd(logp.data_ptr(), ld, action.data_ptr(), weight.data_ptr(), _p(logq), float(clip),
+                                                 _p(ent_weight), gscale.data_ptr(), drow.data_ptr(), dlogp.data_ptr(), ldg, rows, V,
+                                                 stream()), "bmhrl_policy_loss_bwd")

@@ -278,6 +278,14 @@ class _DeviceScorer:
         self.counter += 1
         return delta, scores
 
+    def prefix_scores(self, pred, captions: Sequence[str]) -> Tensor:
+        """the fp64 per-prefix score table (rows, L) of the token rows pred (rows, L) against `captions`, one reference per
+        row (bound first).  Every scorer built on this class has it, the METEOR scorer included (its encode / _score)."""
+        if isinstance(captions, str):
+            raise TypeError("prefix_scores: captions must be a sequence of strings, one per row")
+        self.bind(list(captions))
+        return self._launch(pred)[1]
+
     def reward_fn(self):
         """(sampled (B, L), captions) -> (B, L) fp32 discounted worker reward, as delta_*_worker.  captions: a list of
         strings (bound first) or None (the last bound captions: CaptionTrainer._rl_loss passes None).  Graph-safe: the

@@ -997,6 +997,63 @@ int bmhrl_tiou_pairs(const double* pred_seg, int32_t n_pred, const double* ref_s
                      const int32_t* groups, const int64_t* out_off, int32_t G, double tiou, const int64_t* pair_off,
                      int64_t n_slots, int32_t* pair_ref, int64_t n_pairs, bmhrl_stream_t stream);
 
+/* ---- self-critical policy gradient on sampled rollouts (csrc/policy_loss.hip) ----------------------
+ * bmhrl_rollout_advantage: rollouts and the reward launch's per-prefix table -> per-token weights, nothing read on the host.
+ *  toks (B * n, ldt) int64, sample-major (the n rollouts of clip b are rows b * n .. b * n + n - 1), column 0 the start
+ *  token, columns 1 .. m the generated tokens (a row holds the pad token after its first end_idx); scores (B * n, m) fp64
+ *  with row stride lds: the per-prefix scores of toks[:, 1:]; base (B) fp64, read with BMHRL_BASELINE_GIVEN only.
+ *   R1. len_i = 1 + the index of the first end_idx in toks[i, 1 : m + 1], or m without one;
+ *   R2. r_i = scores[i, len_i - 1], a copy of the fp64 word (whether the end token counts as a word is the scorer's business);
+ *   R3. baseline, fp64 without FMA contraction: LEAVE_ONE_OUT b_i = (sum of r_j over the clip's rollouts j != i, j
+ *       ascending, from 0.0) / (n - 1); GIVEN b_i = base[clip]; NONE b_i = 0;
+ *   R4. adv_i = r_i - b_i;
+ *   R5. N = sum of len_i, an integer;
+ *   R6. weight[i, t] = (float)(adv_i / (double)N) for t < len_i, else +0.0f;
+ *   R7. stats[0..3] = mean r, mean b, mean len, N as fp64: the sums of r and of b run in row order from 0.0 and are divided
+ *       once by (double)(B * n); mean len = (double)N / (double)(B * n).
+ *  Writes len (B * n) int32, reward and adv (B * n) fp64, weight (B * n, m) fp32 with row stride ldw (columns m .. ldw are
+ *  never written) and stats (4) fp64.  One block; every sum has one owner that adds in the order above, so equal inputs give
+ *  equal bits and a host restatement of R1-R7 gives the same bits.  Refused with -22: a null required pointer, n outside
+ *  [1, BMHRL_ROLLOUT_MAX_N], m outside [1, BMHRL_REWARDS_MAX_L], B < 1, LEAVE_ONE_OUT with n == 1, GIVEN without base, an
+ *  unknown baseline, ldt < m + 1, lds < m, ldw < m.
+ *
+ * bmhrl_policy_loss_fwd / bmhrl_policy_loss_bwd: the loss on the log-probs of the training forward.  Per row i of logp
+ *  (rows, V) fp32 with row stride ld: the action a_i (int64), the weight w_i (fp32, the advantage's sign), optionally
+ *  logq_i (fp32, the rollout's log-prob of a_i) with the clip eps, optionally the entropy weight beta_i (fp32, already masked
+ *  and normalised).
+ *   policy term, clip off (eps == 0 and logq null):  l_i = -w_i logp[i, a_i],  d l_i / d logp[i, a_i] = -w_i;
+ *   policy term, clip on (eps > 0 and logq given):   rho = exp(logp[i, a_i] - logq_i),
+ *       l_i = -min(rho w_i, clamp(rho, 1 - eps, 1 + eps) w_i); the gradient at a_i is -rho w_i where the unclipped branch is
+ *       the minimum (ties included), else 0;
+ *   entropy term (ent_weight given): H_i = -sum_v p_v logp_v, p_v = exp(logp_v), a column at -inf contributing 0 to the value
+ *       and to the gradient; the row loss gains -beta_i H_i and the gradient beta_i p_v (1 + logp_v) at every column.  The
+ *       log-probs are independent variables here (the head's own log-softmax backward does the rest).
+ *  An action outside [0, V) makes the row contribute nothing: its row loss is 0 and its gradient row is all zeros.
+ *  fwd writes row_loss (rows) and row_entropy (rows) (H_i with ent_weight, action in range or not; 0 without it).
+ *  bwd writes the dense gradient dlogp (rows, V) fp32 with row stride ldg, every entry times gscale[0] * drow[i] (both fp32,
+ *  device), in one pass: without ent_weight zeros and one entry per row.  Columns V .. ld / ldg are never written.  No
+ *  atomics: equal inputs give equal bits.
+ *  Dispatch.  fwd without ent_weight: a gather, one thread per row.  fwd with ent_weight: one 256-thread block per row, the
+ *  16-byte path when V % 4 == 0, ld % 4 == 0 and logp is 16-byte aligned, else the scalar path.  bwd: one 256-thread block
+ *  per row, the 16-byte path when V % 4 == 0, ld % 4 == 0, ldg % 4 == 0 and logp and dlogp are 16-byte aligned, else the
+ *  scalar path (any V on either).
+ *  Refused with -22: a null required pointer (gscale and drow are required), rows < 1, V < 1, ld < V, ldg < V, eps < 0 or
+ *  NaN, and exactly one of eps > 0 / logq given.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_ROLLOUT_MAX_N 16
+#define BMHRL_BASELINE_NONE 0
+#define BMHRL_BASELINE_LEAVE_ONE_OUT 1
+#define BMHRL_BASELINE_GIVEN 2
+int bmhrl_rollout_advantage(const int64_t* toks, int64_t ldt, int32_t B, int32_t n, int32_t m, int64_t end_idx,
+                            const double* scores, int64_t lds, int32_t baseline, const double* base, int32_t* len, double* reward,
+                            double* adv, float* weight, int64_t ldw, double* stats, bmhrl_stream_t stream);
+int bmhrl_policy_loss_fwd(const float* logp, int64_t ld, const int64_t* action, const float* weight, const float* logq, float clip,
+                          const float* ent_weight, float* row_loss, float* row_entropy, int64_t rows, int32_t V,
+                          bmhrl_stream_t stream);
+int bmhrl_policy_loss_bwd(const float* logp, int64_t ld, const int64_t* action, const float* weight, const float* logq, float clip,
+                          const float* ent_weight, const float* gscale, const float* drow, float* dlogp, int64_t ldg, int64_t rows,
+                          int32_t V, bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
