@@ -48,19 +48,18 @@ class GemmDesc(C.Structure):
     ]
 
 
-# name -> argtypes (every entry point of include/bmhrl_hip.h; tests check the .so exports all of them)
+# The two tables below name every entry point of include/bmhrl_hip.h (tests check the .so exports all of them).
+# PROTOTYPES: name -> argtypes of the entries that launch on a stream: they return int (0, -EINVAL or a hipError_t) and
+# their last argument is the stream.
 PROTOTYPES = {
     "bmhrl_gemm": [C.POINTER(GemmDesc), ptr],
     "bmhrl_gemm_group": [C.POINTER(GemmDesc), i32, ptr],
-    "bmhrl_gemm_f32_fast_path": [C.POINTER(GemmDesc)],
     "bmhrl_attention_fwd": [ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, i64, i64, i32, i32, i32, i32, i32, f32,
                             f32, u64, ptr, ptr],
     "bmhrl_attention_shared128_fwd": [ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, i64, i32, i32, i32, i32, f32, ptr],
     "bmhrl_attention_fwd_f16": [ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, i64, i64, i32, i32, i32, i32, i32, f32,
                                 f32, u64, ptr, ptr],
     "bmhrl_attention_shared128_fwd_f16": [ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, i64, i32, i32, i32, i32, f32, ptr],
-    "bmhrl_attention_config": [i32, i32],
-    "bmhrl_attention_plan": [i32, i32, i32, i32, i32, i64],
     "bmhrl_attention_shared128_bwd": [ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr, i64, ptr, i64, ptr, i64, i32, ptr, i32, i32,
                                       i32, i32, f32, ptr],
     "bmhrl_small_attention_fwd": [ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, i32, ptr, i64, i64, i32, i32, i32, i32, i32, f32, f32,
@@ -73,7 +72,6 @@ PROTOTYPES = {
     "bmhrl_softmax_rows": [ptr, i64, ptr, i64, i64, i32, i32, i64, ptr],
     "bmhrl_softmax_bwd_rows": [ptr, i64, ptr, i64, ptr, i64, i64, i32, f32, ptr, i64, i64, i32, i32, i32, i64, ptr],
     "bmhrl_attn_delta": [ptr, i64, ptr, i64, ptr, f32, i32, i32, i32, i32, ptr],
-    "bmhrl_attention_bwd_scores256_ok": [i32, i32, i32, i64],
     "bmhrl_attention_bwd_scores256": [ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, i64, ptr, ptr, i64, i32, i32, i32, i32,
                                       f32, ptr],
     "bmhrl_layernorm_fwd": [ptr, ptr, ptr, ptr, i64, ptr, ptr, ptr, i64, i32, ptr],
@@ -165,6 +163,36 @@ PROTOTYPES = {
     "bmhrl_policy_loss_bwd": [ptr, i64, ptr, ptr, ptr, f32, ptr, ptr, ptr, ptr, i64, i64, i32, ptr],
 }
 
+# QUERIES: name -> (restype, argtypes) of the host-only entries (plans, limits, workspace sizes, build facts): no stream,
+# nothing is launched.
+QUERIES = {
+    "bmhrl_hip_arch": (C.c_char_p, []),
+    "bmhrl_hip_abi_version": (C.c_int, []),
+    "bmhrl_deterministic_enabled": (C.c_int, []),
+    "bmhrl_layernorm_bwd_workspace": (C.c_int64, [i64, i32]),
+    "bmhrl_attention_shared128_bwd_workspace": (C.c_int64, [i32, i32, i32]),
+    "bmhrl_attention_max_keys": (C.c_int, []),
+    "bmhrl_attention_config": (C.c_int, [i32, i32]),
+    "bmhrl_attention_plan": (C.c_int, [i32, i32, i32, i32, i32, i64]),
+    "bmhrl_attention_bwd_scores256_ok": (C.c_int, [i32, i32, i32, i64]),
+    "bmhrl_memory_attention_ok": (C.c_int, [i32, i32, i32]),
+    "bmhrl_small_attention_ok": (C.c_int, [i32, i32, i32]),
+    "bmhrl_gemm_splits": (C.c_int, [i32, i32, i32, i32]),
+    "bmhrl_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(i32)]),
+    "bmhrl_gemm_group_plan": (C.c_int, [C.POINTER(GemmDesc), i32]),
+    "bmhrl_gemm_f32_fast_path": (C.c_int, [C.POINTER(GemmDesc)]),
+}
+
+
+def _is_pointer(t) -> bool:
+    return t is ptr or isinstance(t, type(C.POINTER(i32)))
+
+
+# name -> the argument positions that take an address (c_void_p or POINTER(...)), of both tables; derived, never written
+# by hand.  For a PROTOTYPES entry the last one is the stream.
+PTR_SLOTS = {name: tuple(i for i, t in enumerate(argtypes) if _is_pointer(t))
+             for name, argtypes in [*PROTOTYPES.items(), *((name, q[1]) for name, q in QUERIES.items())]}
+
 _lib = None
 
 
@@ -184,32 +212,20 @@ def load() -> C.CDLL:
     if os.path.exists(hip_rt):
         C.CDLL(hip_rt, mode=C.RTLD_GLOBAL)
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in PROTOTYPES.items():
+
+    def bind(name, restype, argtypes):
         try:
             fn = getattr(lib, name)
         except AttributeError:      # (functions are added without a new ABI version: name the stale build, not just the symbol)
             raise RuntimeError(f"{LIB_PATH} does not export {name}: it was built from older sources than this package; "
                                "rebuild it with `python -m bmhrl_amd.build`") from None
         fn.argtypes = argtypes
-        fn.restype = C.c_int
-    lib.bmhrl_layernorm_bwd_workspace.argtypes = [i64, i32]
-    lib.bmhrl_layernorm_bwd_workspace.restype = C.c_int64
-    lib.bmhrl_attention_shared128_bwd_workspace.argtypes = [i32, i32, i32]
-    lib.bmhrl_attention_shared128_bwd_workspace.restype = C.c_int64
-    lib.bmhrl_attention_max_keys.restype = C.c_int
-    lib.bmhrl_memory_attention_ok.argtypes = [i32, i32, i32]
-    lib.bmhrl_memory_attention_ok.restype = C.c_int
-    lib.bmhrl_small_attention_ok.argtypes = [i32, i32, i32]
-    lib.bmhrl_small_attention_ok.restype = C.c_int
-    lib.bmhrl_gemm_splits.argtypes = [i32, i32, i32, i32]
-    lib.bmhrl_gemm_splits.restype = C.c_int
-    lib.bmhrl_gemm_plan.argtypes = [C.POINTER(GemmDesc), C.POINTER(i32)]
-    lib.bmhrl_gemm_plan.restype = C.c_int
-    lib.bmhrl_gemm_group_plan.argtypes = [C.POINTER(GemmDesc), i32]
-    lib.bmhrl_gemm_group_plan.restype = C.c_int
-    lib.bmhrl_hip_arch.restype = C.c_char_p
-    lib.bmhrl_hip_abi_version.restype = C.c_int
-    lib.bmhrl_deterministic_enabled.restype = C.c_int
+        fn.restype = restype
+
+    for name, argtypes in PROTOTYPES.items():
+        bind(name, C.c_int, argtypes)
+    for name, (restype, argtypes) in QUERIES.items():
+        bind(name, restype, argtypes)
     _lib = lib
     return lib
 

@@ -2203,7 +2203,6 @@ class SegmentCriticFn(torch.autograd.Function):
         if len(args) not in (30, 33):
             raise TypeError("SegmentCriticFn takes emb, 30 parameters and optionally labels, mask, pos_weight")
         params, extra = args[:30], args[30:]
-        ops._need_cuda(emb, *params)
         B, L, d = emb.shape
         rows, H, dev = B * L, params[1].shape[1], emb.device
         x = emb.detach().float().contiguous().view(rows, d)
@@ -2231,7 +2230,6 @@ class SegmentCriticFn(torch.autograd.Function):
         ctx.with_loss = bool(extra)
         if extra:
             labels, mask, pw = extra
-            ops._need_cuda(labels, mask)
             labels = labels.detach().float().contiguous()
             mask = mask.detach().to(torch.bool).contiguous()
             loss = torch.empty((), device=dev)

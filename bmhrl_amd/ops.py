@@ -1,5 +1,9 @@
 """Thin torch-tensor wrappers over the C ABI (include/bmhrl_hip.h).  Tensors only lend their device pointers;
-every call is enqueued on torch's current HIP stream.  No wrapper has a CPU path."""
+every call is enqueued on torch's current HIP stream.  No wrapper has a CPU path.
+
+Every call into the library goes through _launch (the entries of _lib.PROTOTYPES: a stream is appended) or _query (the
+host-only entries of _lib.QUERIES), and every address comes from _ptr / _at: a CPU tensor, a tensor where a number
+belongs or a wrong argument count is refused there, before the library is touched."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,9 +19,80 @@ from . import _lib
 EPI_LINEAR, EPI_PROB, EPI_DSCORE, EPI_RELU_BWD = 0, 1, 2, 3
 
 
+def pad8(n: int) -> int:
+    return (n + 7) & ~7
+
+
+def stream() -> int:
+    """torch's current HIP stream on the current device as the handle the C ABI takes: the value of
+    torch.cuda.current_stream().cuda_stream without building the Stream object (2.6 us against 0.3 per launch)"""
+    return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device())
+
+
+_Tensor, _Parameter = torch.Tensor, torch.nn.Parameter
+_TENSORS = frozenset((_Tensor, _Parameter))
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    """the device address of t (None stays None): the one place a tensor lends its pointer, and it refuses CPU memory (an
+    empty tensor has none: it lends the null pointer whatever its device)"""
+    if t is None:
+        return None
+    if not t.is_cuda and t.data_ptr():
+        raise RuntimeError("bmhrl_amd ops run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    return t.data_ptr()
+
+
+def _at(t: Optional[torch.Tensor], off: int):
+    """the device address of element `off` of t (None stays None)"""
+    p = _ptr(t)
+    return p + off * t.element_size() if off and p is not None else p
+
+
+# name -> (arguments without the stream, their pointer slots) of the launching entries, from the tables of _lib
+_LAUNCH = {name: (len(argtypes) - 1, _lib.PTR_SLOTS[name][:-1]) for name, argtypes in _lib.PROTOTYPES.items()}
+
+
+def _launch(name: str, *args) -> None:
+    """enqueue entry `name` of _lib.PROTOTYPES on the current stream: the tensors in its pointer slots become device addresses
+    (None, ints and ctypes objects pass as they are), a tensor anywhere else is an error; raises _lib.HipError when the
+    library refuses.  Every eager launch pays for this: only the pointer slots are walked in Python, exact types first,
+    and what is left of the list gets one scan for a stray tensor (a Tensor or a Parameter; any other subclass at an
+    integer's position is ctypes' own argument error)."""
+    n, slots = _LAUNCH[name]
+    if len(args) != n:
+        raise TypeError(f"{name} takes {n} arguments and the stream, got {len(args)}")
+    a = list(args)
+    for i in slots:
+        v = a[i]
+        t = type(v)
+        if t is _Tensor or t is _Parameter or (t is not int and v is not None and isinstance(v, _Tensor)):
+            a[i] = _ptr(v)
+    if not _TENSORS.isdisjoint(map(type, a)):
+        i = next(i for i, v in enumerate(a) if isinstance(v, _Tensor))
+        raise TypeError(f"{name}: argument {i} is a number, got a tensor")
+    a.append(stream())          # (after the refusals: they need neither the stream nor the library)
+    _lib.check(getattr(_lib.load(), name)(*a), name)
+
+
+def _query(name: str, *args, refusal: bool = True):
+    """the value of the host-only entry `name` of _lib.QUERIES (numbers and descriptors in, no stream, no tensor);
+    refusal: a negative int is the library refusing the arguments (raises _lib.HipError), not a value"""
+    restype, argtypes = _lib.QUERIES[name]
+    if len(args) != len(argtypes):
+        raise TypeError(f"{name} takes {len(argtypes)} arguments, got {len(args)}")
+    for i, v in enumerate(args):
+        if isinstance(v, _Tensor):
+            raise TypeError(f"{name}: argument {i} is a number or a descriptor, got a tensor")
+    r = getattr(_lib.load(), name)(*args)
+    if refusal and restype is C.c_int and r < 0:
+        _lib.check(r, name)
+    return r
+
+
 def attention_max_keys() -> int:
     """largest Sk of the fused attention kernels (bmhrl_attention_max_keys)"""
-    return _lib.load().bmhrl_attention_max_keys()
+    return _query("bmhrl_attention_max_keys")
 
 
 ATTN_PLAN_KINDS = {"256-fwd": 0, "128-fwd": 1, "128-bwd": 2}
@@ -26,25 +101,7 @@ ATTN_PLAN_KINDS = {"256-fwd": 0, "128-fwd": 1, "128-bwd": 2}
 def attention_plan(kind: str, B: int, H: int, Sq: int, Sk: int, mask_sq: int = 0) -> int:
     """the kernel code the entry `kind` would take for this shape under the current bmhrl_attention_config pin (pure host
     query: bmhrl_attention_plan); negative for a shape the entry refuses"""
-    return int(_lib.load().bmhrl_attention_plan(ATTN_PLAN_KINDS[kind], B, H, Sq, Sk, mask_sq))
-
-
-def pad8(n: int) -> int:
-    return (n + 7) & ~7
-
-
-def stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _need_cuda(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("bmhrl_amd ops run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    return int(_query("bmhrl_attention_plan", ATTN_PLAN_KINDS[kind], B, H, Sq, Sk, mask_sq, refusal=False))
 
 
 def bf16_zeros(rows: int, cols: int, device) -> torch.Tensor:
@@ -64,55 +121,42 @@ def gemm_desc(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda: 
               colsum: Optional[torch.Tensor] = None, colsum_off=0, colsum_sb2=0, bias_sb2=0, colsum_sb1=0, bias_sb1=0,
               split_ws: Optional[torch.Tensor] = None) -> "_lib.GemmDesc":
     """the bmhrl_gemm_desc of gemm(...) with the same arguments (defer aside); the tensors must outlive its use"""
-    _need_cuda(A, B, C_f32, C_bf16)
     d = _lib.GemmDesc()
     d.M, d.N, d.K = M, N, K
     d.batch1, d.batch2 = batch
-    d.A = A.data_ptr() + 2 * a_off; d.lda = lda; d.a_sb1, d.a_sb2 = a_strides; d.a_trans = int(a_trans)
-    d.B = B.data_ptr() + 2 * b_off; d.ldb = ldb; d.b_sb1, d.b_sb2 = b_strides; d.b_trans = int(b_trans)
-    d.C = None if C_f32 is None else C_f32.data_ptr() + 4 * c_off; d.ldc = ldc; d.c_sb1, d.c_sb2 = c_strides
-    d.Cb = None if C_bf16 is None else C_bf16.data_ptr() + 2 * cb_off; d.ldcb = ldcb; d.cb_sb1, d.cb_sb2 = cb_strides
+    d.A = _at(A, a_off); d.lda = lda; d.a_sb1, d.a_sb2 = a_strides; d.a_trans = int(a_trans)
+    d.B = _at(B, b_off); d.ldb = ldb; d.b_sb1, d.b_sb2 = b_strides; d.b_trans = int(b_trans)
+    d.C = _at(C_f32, c_off); d.ldc = ldc; d.c_sb1, d.c_sb2 = c_strides
+    d.Cb = _at(C_bf16, cb_off); d.ldcb = ldcb; d.cb_sb1, d.cb_sb2 = cb_strides
     d.epilogue = epilogue; d.alpha = alpha; d.relu = int(relu); d.accumulate = int(accumulate)
     d.allow_split_k = int(allow_split_k)
-    d.bias = _p(bias)
-    d.residual = _p(residual); d.ldr = ldr; d.r_sb1, d.r_sb2 = r_strides
-    d.mask = _p(mask); d.mask_sb1 = mask_sb1; d.mask_sm = mask_sm
-    d.rowvec = _p(rowvec); d.rowvec2 = _p(rowvec2); d.rv_sb1, d.rv_sb2 = rv_strides
-    d.aux = None if aux is None else aux.data_ptr() + 2 * aux_off; d.ldaux = ldaux; d.aux_sb1, d.aux_sb2 = aux_strides
-    d.dropout_p = dropout_p; d.seed = seed; d.seed_dev = _p(seed_dev)
+    d.bias = _ptr(bias)
+    d.residual = _ptr(residual); d.ldr = ldr; d.r_sb1, d.r_sb2 = r_strides
+    d.mask = _ptr(mask); d.mask_sb1 = mask_sb1; d.mask_sm = mask_sm
+    d.rowvec = _ptr(rowvec); d.rowvec2 = _ptr(rowvec2); d.rv_sb1, d.rv_sb2 = rv_strides
+    d.aux = _at(aux, aux_off); d.ldaux = ldaux; d.aux_sb1, d.aux_sb2 = aux_strides
+    d.dropout_p = dropout_p; d.seed = seed; d.seed_dev = _ptr(seed_dev)
     d.drop_sb1, d.drop_sb2, d.drop_sm = drop_strides
-    d.colsum = None if colsum is None else colsum.data_ptr() + 4 * colsum_off; d.colsum_sb2 = colsum_sb2
+    d.colsum = _at(colsum, colsum_off); d.colsum_sb2 = colsum_sb2
     d.bias_sb2 = bias_sb2; d.bias_sb1 = bias_sb1; d.colsum_sb1 = colsum_sb1
-    d.split_ws = _p(split_ws); d.split_ws_elems = 0 if split_ws is None else split_ws.numel()
+    d.split_ws = _ptr(split_ws); d.split_ws_elems = 0 if split_ws is None else split_ws.numel()
     return d
 
 
-def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda: int, ldb: int, a_trans=False, b_trans=False,
-         batch: Tuple[int, int] = (1, 1), a_strides=(0, 0), b_strides=(0, 0), a_off=0, b_off=0,
-         C_f32: Optional[torch.Tensor] = None, ldc=0, c_strides=(0, 0), c_off=0,
-         C_bf16: Optional[torch.Tensor] = None, ldcb=0, cb_strides=(0, 0), cb_off=0,
-         epilogue=EPI_LINEAR, alpha=1.0, relu=False, accumulate=False, bias=None, residual=None, ldr=0,
-         r_strides=(0, 0), mask=None, mask_sb1=0, mask_sm=0, rowvec=None, rowvec2=None, rv_strides=(0, 0),
-         aux=None, ldaux=0, aux_strides=(0, 0), aux_off=0, dropout_p=0.0, seed=0, seed_dev=None, drop_strides=(0, 0, 0), allow_split_k=False,
-         colsum: Optional[torch.Tensor] = None, colsum_off=0, colsum_sb2=0, bias_sb2=0, colsum_sb1=0, bias_sb1=0,
-         defer: Optional[list] = None, split_ws: Optional[torch.Tensor] = None) -> None:
-    """C[b] = epilogue(A[b] @ B[b]); offsets are in elements from the tensors' data pointers.
+_GEMM_OPERANDS = ("C_f32", "C_bf16", "bias", "residual", "mask", "rowvec", "rowvec2", "aux", "seed_dev", "colsum")
+
+
+def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, defer: Optional[list] = None, **desc) -> None:
+    """C[b] = epilogue(A[b] @ B[b]); **desc: the keywords of gemm_desc; offsets are in elements from the tensors' data pointers.
     split_ws: fp32 workspace of >= gemm_splits(M, N, K, batch) * batch * M * N elements: a K split then runs as partial tiles +
     an ordered second pass instead of fp32 atomics (reproducible; C needs no zeroing).
     defer: a list -- the problem is appended to it instead of launched; gemm_flush(list) then launches up to four of them as
     ONE kernel (bmhrl_gemm_group: leaf products nothing in between depends on)."""
-    d = gemm_desc(A, B, M, N, K, lda=lda, ldb=ldb, a_trans=a_trans, b_trans=b_trans, batch=batch, a_strides=a_strides,
-                  b_strides=b_strides, a_off=a_off, b_off=b_off, C_f32=C_f32, ldc=ldc, c_strides=c_strides, c_off=c_off,
-                  C_bf16=C_bf16, ldcb=ldcb, cb_strides=cb_strides, cb_off=cb_off, epilogue=epilogue, alpha=alpha, relu=relu,
-                  accumulate=accumulate, bias=bias, residual=residual, ldr=ldr, r_strides=r_strides, mask=mask, mask_sb1=mask_sb1,
-                  mask_sm=mask_sm, rowvec=rowvec, rowvec2=rowvec2, rv_strides=rv_strides, aux=aux, ldaux=ldaux,
-                  aux_strides=aux_strides, aux_off=aux_off, dropout_p=dropout_p, seed=seed, seed_dev=seed_dev,
-                  drop_strides=drop_strides, allow_split_k=allow_split_k, colsum=colsum, colsum_off=colsum_off,
-                  colsum_sb2=colsum_sb2, bias_sb2=bias_sb2, colsum_sb1=colsum_sb1, bias_sb1=bias_sb1, split_ws=split_ws)
+    d = gemm_desc(A, B, M, N, K, **desc)
     if defer is not None and _GROUP_LEAVES:
-        defer.append((d, (A, B, C_f32, C_bf16, bias, residual, mask, rowvec, rowvec2, aux, seed_dev, colsum)))   # (operands kept alive)
+        defer.append((d, (A, B, *map(desc.get, _GEMM_OPERANDS))))   # (operands kept alive)
         return
-    _lib.check(_lib.load().bmhrl_gemm(C.byref(d), stream()), "bmhrl_gemm")
+    _launch("bmhrl_gemm", C.byref(d))
 
 
 GEMM_PLAN_FIELDS = ("loop", "tile", "stages", "splits", "split_form", "epi_path", "vec_ok", "ordered_colsum")
@@ -122,26 +166,19 @@ def gemm_plan(d: "_lib.GemmDesc") -> dict:
     """what bmhrl_gemm launches for descriptor d (bmhrl_gemm_plan: the launcher's own decision, host only) as a dict of
     GEMM_PLAN_FIELDS; raises for a descriptor bmhrl_gemm refuses"""
     plan = (_lib.i32 * 8)()
-    _lib.check(_lib.load().bmhrl_gemm_plan(C.byref(d), plan), "bmhrl_gemm_plan")
+    _lib.check(_query("bmhrl_gemm_plan", C.byref(d), plan), "bmhrl_gemm_plan")
     return dict(zip(GEMM_PLAN_FIELDS, plan))
 
 
 def gemm_f32_fast_path(d: "_lib.GemmDesc") -> bool:
     """True when the interior tiles of d's fp32 output leave through the specialised fp32 epilogue (bmhrl_gemm_f32_fast_path;
     gemm_plan reports such a launch as epi_path "generic"); raises for a descriptor bmhrl_gemm refuses"""
-    r = int(_lib.load().bmhrl_gemm_f32_fast_path(C.byref(d)))
-    if r < 0:
-        _lib.check(r, "bmhrl_gemm_f32_fast_path")
-    return bool(r)
+    return bool(_query("bmhrl_gemm_f32_fast_path", C.byref(d)))
 
 
 def gemm_group_plan(descs) -> int:
     """gemm_group_kernel launches bmhrl_gemm_group makes for these descriptors (0: one by one); raises on a refused one"""
-    arr = (_lib.GemmDesc * len(descs))(*descs)
-    r = int(_lib.load().bmhrl_gemm_group_plan(arr, len(descs)))
-    if r < 0:
-        _lib.check(r, "bmhrl_gemm_group_plan")
-    return r
+    return int(_query("bmhrl_gemm_group_plan", (_lib.GemmDesc * len(descs))(*descs), len(descs)))
 
 
 _GROUP_LEAVES = os.environ.get("BMHRL_GEMM_GROUP", "1") == "1"      # (A/B switch: 0 launches deferred problems at once)
@@ -152,8 +189,7 @@ def gemm_flush(deferred: list) -> None:
     kernel variant, one by one otherwise (bmhrl_gemm_group decides)"""
     if not deferred:
         return
-    arr = (_lib.GemmDesc * len(deferred))(*[d for d, _ in deferred])
-    _lib.check(_lib.load().bmhrl_gemm_group(arr, len(deferred), stream()), "bmhrl_gemm_group")
+    _launch("bmhrl_gemm_group", (_lib.GemmDesc * len(deferred))(*[d for d, _ in deferred]), len(deferred))
     deferred.clear()
 
 
@@ -162,54 +198,41 @@ _SPLITS = {}
 
 def gemm_splits(M: int, N: int, K: int, batch: int = 1) -> int:
     """K splits the launcher uses for a plain fp32 (M, N) output over a reduction of K with allow_split_k (bmhrl_gemm_splits)"""
-    key = (M, N, K, batch, "n")
+    key = (M, N, K, batch)
     r = _SPLITS.get(key)
     if r is None:
-        r = _SPLITS[key] = int(_lib.load().bmhrl_gemm_splits(M, N, K, batch))
+        r = int(_query("bmhrl_gemm_splits", M, N, K, batch, refusal=False))
         if r < 1:
-            raise RuntimeError(f"bmhrl_gemm_splits{key[:4]} failed: {r}")
+            raise RuntimeError(f"bmhrl_gemm_splits{key} failed: {r}")
+        _SPLITS[key] = r
     return r
 
 
 def gemm_overwrites(M: int, N: int, K: int, batch: int = 1) -> bool:
     """True when gemm(..., C_f32=..., allow_split_k=True) of this shape stores every element of C exactly once (no K
     split, no atomics): the output may then be uninitialised memory.  The launcher's own decision (bmhrl_gemm_splits)."""
-    key = (M, N, K, batch)
-    r = _SPLITS.get(key)
-    if r is None:
-        n = int(_lib.load().bmhrl_gemm_splits(M, N, K, batch))
-        if n < 1:
-            raise RuntimeError(f"bmhrl_gemm_splits{key} failed: {n}")
-        r = _SPLITS[key] = n == 1
-    return r
+    return gemm_splits(M, N, K, batch) == 1
 
 
 def attention_fwd(Q, K, V, O, row_max, row_sum, mask, mask_sb, mask_sq, B, H, Sq, Sk, dk, scale, ldq, ldk, ldv, ldo,
                   q_off=0, k_off=0, v_off=0, dropout_p=0.0, seed=0, seed_dev=None):
-    _need_cuda(Q, K, V, O)
     f16 = Q.dtype == torch.float16          # IEEE-half operands: the fp16 build of the same kernel
     if any((t.dtype == torch.float16) != f16 for t in (K, V, O)):
         raise RuntimeError("attention_fwd: Q, K, V and O must share one 16-bit type")
-    fn = _lib.load().bmhrl_attention_fwd_f16 if f16 else _lib.load().bmhrl_attention_fwd
-    _lib.check(fn(Q.data_ptr() + 2 * q_off, ldq, K.data_ptr() + 2 * k_off, ldk,
-                                               V.data_ptr() + 2 * v_off, ldv, O.data_ptr(), ldo, row_max.data_ptr(),
-                                               row_sum.data_ptr(), _p(mask), mask_sb, mask_sq, B, H, Sq, Sk, dk, scale,
-                                               dropout_p, seed, _p(seed_dev), stream()), "bmhrl_attention_fwd")
+    _launch("bmhrl_attention_fwd_f16" if f16 else "bmhrl_attention_fwd", _at(Q, q_off), ldq, _at(K, k_off), ldk, _at(V, v_off),
+            ldv, O, ldo, row_max, row_sum, mask, mask_sb, mask_sq, B, H, Sq, Sk, dk, scale, dropout_p, seed, seed_dev)
 
 
 def small_attention_ok(Sq: int, Sk: int, dk: int) -> bool:
     """shapes bmhrl_small_attention_fwd / _bwd serve (pure host query)"""
-    return bool(_lib.load().bmhrl_small_attention_ok(Sq, Sk, dk))
+    return bool(_query("bmhrl_small_attention_ok", Sq, Sk, dk))
 
 
 def small_attention_fwd(Q, K, V, O, P, ldp, mask, mask_sb, mask_sq, B, H, Sq, Sk, dk, scale, ldq, ldk, ldv, ldo,
                         q_off=0, k_off=0, v_off=0, dropout_p=0.0, seed=0, seed_dev=None):
     """one launch: O (bf16 [B*Sq, ldo]) = dropout(softmax(scale Q K^T, masked) V), P (bf16 (B, H, Sq, ldp)) kept for backward"""
-    _need_cuda(Q, K, V, O, P)
-    _lib.check(_lib.load().bmhrl_small_attention_fwd(Q.data_ptr() + 2 * q_off, ldq, K.data_ptr() + 2 * k_off, ldk,
-                                                     V.data_ptr() + 2 * v_off, ldv, O.data_ptr(), ldo, P.data_ptr(), ldp, _p(mask),
-                                                     mask_sb, mask_sq, B, H, Sq, Sk, dk, scale, dropout_p, seed, _p(seed_dev),
-                                                     stream()), "bmhrl_small_attention_fwd")
+    _launch("bmhrl_small_attention_fwd", _at(Q, q_off), ldq, _at(K, k_off), ldk, _at(V, v_off), ldv, O, ldo, P, ldp, mask,
+            mask_sb, mask_sq, B, H, Sq, Sk, dk, scale, dropout_p, seed, seed_dev)
 
 
 def small_attention_bwd(dO, lddo, P, ldp, Q, K, V, dQ, dK, dV, mask, mask_sb, mask_sq, B, H, Sq, Sk, dk, scale, ldq, ldk, ldv,
@@ -217,120 +240,92 @@ def small_attention_bwd(dO, lddo, P, ldp, Q, K, V, dQ, dK, dV, mask, mask_sb, ma
                         dbq_off=0, dbk_off=0, dbv_off=0):
     """one launch: dQ / dK / dV (bf16, written into column slices) and optionally the bias gradients dbq / dbk / dbv
     (fp32 (H * dk) at the given element offsets, added to)"""
-    _need_cuda(dO, P, Q, K, V, dQ, dK, dV)
-    fp = lambda t, off: None if t is None else t.data_ptr() + 4 * off
-    _lib.check(_lib.load().bmhrl_small_attention_bwd(dO.data_ptr(), lddo, P.data_ptr(), ldp, Q.data_ptr() + 2 * q_off, ldq,
-                                                     K.data_ptr() + 2 * k_off, ldk, V.data_ptr() + 2 * v_off, ldv,
-                                                     dQ.data_ptr() + 2 * dq_off, lddq, dK.data_ptr() + 2 * dk_off, lddk,
-                                                     dV.data_ptr() + 2 * dv_off, lddv, fp(dbq, dbq_off), fp(dbk, dbk_off),
-                                                     fp(dbv, dbv_off), _p(mask), mask_sb, mask_sq, B, H, Sq, Sk, dk, scale,
-                                                     stream()), "bmhrl_small_attention_bwd")
+    _launch("bmhrl_small_attention_bwd", dO, lddo, P, ldp, _at(Q, q_off), ldq, _at(K, k_off), ldk, _at(V, v_off), ldv,
+            _at(dQ, dq_off), lddq, _at(dK, dk_off), lddk, _at(dV, dv_off), lddv, _at(dbq, dbq_off), _at(dbk, dbk_off),
+            _at(dbv, dbv_off), mask, mask_sb, mask_sq, B, H, Sq, Sk, dk, scale)
 
 
 def memory_attention_ok(L: int, Sk: int, dm: int) -> bool:
     """shapes bmhrl_memory_attention serves (pure host query)"""
-    return bool(_lib.load().bmhrl_memory_attention_ok(L, Sk, dm))
+    return bool(_query("bmhrl_memory_attention_ok", L, Sk, dm))
 
 
 def cast_memory(x, y, y_t, B, Sk, dm, ldt):
     """fp32 memory (B * Sk, dm) -> bf16 copy y (B * Sk, dm) and per-sample transposed copy y_t (B, dm, ldt), one launch"""
-    _need_cuda(x, y, y_t)
-    _lib.check(_lib.load().bmhrl_cast_memory(x.data_ptr(), y.data_ptr(), y_t.data_ptr(), B, Sk, dm, ldt, stream()), "bmhrl_cast_memory")
+    _launch("bmhrl_cast_memory", x, y, y_t, B, Sk, dm, ldt)
 
 
 def memory_attention(backward, X, x_off, ldx, mem, mem_t, ldt, PD, pd_row, pd_slot, Y, ldy, mask, mask_sb, n_mem, B2, H, L, Sk, dm,
                      scale):
     """few-query attention core over a memory, one launch (see bmhrl_memory_attention in include/bmhrl_hip.h)"""
-    _need_cuda(X, mem, mem_t, PD, Y)
-    _lib.check(_lib.load().bmhrl_memory_attention(int(backward), X.data_ptr() + 2 * x_off, ldx, mem.data_ptr(), Sk * dm,
-                                                  mem_t.data_ptr(), dm * ldt, ldt, PD.data_ptr(), pd_row, pd_slot, Y.data_ptr(), ldy,
-                                                  _p(mask), mask_sb, n_mem, B2, H, L, Sk, dm, scale, stream()),
-               "bmhrl_memory_attention")
+    _launch("bmhrl_memory_attention", int(backward), _at(X, x_off), ldx, mem, Sk * dm, mem_t, dm * ldt, ldt, PD, pd_row, pd_slot,
+            Y, ldy, mask, mask_sb, n_mem, B2, H, L, Sk, dm, scale)
 
 
 def attention_shared128_fwd(Qp, X, ctx, row_max, row_sum, mask, mask_sb, B, H, Sq, Sk, scale, ldq, ldx, ldo):
     """absorbed-projection attention: Qp (B,Sq,H,128), X (B,Sk,128) shared by all heads -> ctx (B,Sq,H,128)"""
-    _need_cuda(Qp, X, ctx)
     f16 = Qp.dtype == torch.float16
     if any((t.dtype == torch.float16) != f16 for t in (X, ctx)):
         raise RuntimeError("attention_shared128_fwd: Qp, X and ctx must share one 16-bit type")
-    fn = _lib.load().bmhrl_attention_shared128_fwd_f16 if f16 else _lib.load().bmhrl_attention_shared128_fwd
-    _lib.check(fn(Qp.data_ptr(), ldq, X.data_ptr(), ldx, ctx.data_ptr(), ldo,
-                                                         row_max.data_ptr(), row_sum.data_ptr(), _p(mask), mask_sb,
-                                                         B, H, Sq, Sk, scale, stream()), "bmhrl_attention_shared128_fwd")
+    _launch("bmhrl_attention_shared128_fwd_f16" if f16 else "bmhrl_attention_shared128_fwd", Qp, ldq, X, ldx, ctx, ldo, row_max,
+            row_sum, mask, mask_sb, B, H, Sq, Sk, scale)
 
 
 def attention_shared128_bwd(Qp, X, dCx, row_max, row_sum, delta, mask, mask_sb, dQp, dX, accumulate_dx, B, H, Sq, Sk, scale,
                             ldq, ldx, lddo, lddq, lddx=128):
     """fused backward of attention_shared128_fwd: dQp (bf16) and, when dX is given, dX (fp32 (B,Sk,128), += when
     accumulate_dx) -- P / dS are recomputed per tile and never written to HBM"""
-    _need_cuda(Qp, X, dCx, dQp)
-    lib = _lib.load()
     ws = None
     if dX is not None:
-        ws = torch.empty(int(lib.bmhrl_attention_shared128_bwd_workspace(B, H, Sk)), device=Qp.device)
-    _lib.check(lib.bmhrl_attention_shared128_bwd(Qp.data_ptr(), ldq, X.data_ptr(), ldx, dCx.data_ptr(), lddo, row_max.data_ptr(),
-                                                 row_sum.data_ptr(), delta.data_ptr(), _p(mask), mask_sb, dQp.data_ptr(), lddq,
-                                                 _p(dX), lddx, int(bool(accumulate_dx)), _p(ws), B, H, Sq, Sk, scale, stream()),
-               "bmhrl_attention_shared128_bwd")
+        ws = torch.empty(int(_query("bmhrl_attention_shared128_bwd_workspace", B, H, Sk)), device=Qp.device)
+    _launch("bmhrl_attention_shared128_bwd", Qp, ldq, X, ldx, dCx, lddo, row_max, row_sum, delta, mask, mask_sb, dQp, lddq, dX,
+            lddx, int(bool(accumulate_dx)), ws, B, H, Sq, Sk, scale)
 
 
 def softmax_bwd_rows(P, ldp, dP, lddp, dS, ldds, rows, cols, scale, mask=None, mask_sb=0, mask_sq=0, rows_per_query=1, queries=1,
                      rows_per_group=0, group_stride=0, p_off=0, ds_off=0):
     """dS = scale * P * (dP - rowsum(P * dP)), 0 at masked keys; P bf16, dP fp32, dS bf16; rows = (sample, query, rows_per_query).
     rows_per_group > 0: P and dS rows in groups of that many, group g at g * group_stride elements (+ p_off / ds_off)"""
-    _need_cuda(P, dP, dS)
-    _lib.check(_lib.load().bmhrl_softmax_bwd_rows(P.data_ptr() + 2 * p_off, ldp, dP.data_ptr(), lddp, dS.data_ptr() + 2 * ds_off, ldds,
-                                                  rows, cols, scale, _p(mask), mask_sb, mask_sq, rows_per_query, queries,
-                                                  rows_per_group, group_stride, stream()), "bmhrl_softmax_bwd_rows")
+    _launch("bmhrl_softmax_bwd_rows", _at(P, p_off), ldp, dP, lddp, _at(dS, ds_off), ldds, rows, cols, scale, mask, mask_sb,
+            mask_sq, rows_per_query, queries, rows_per_group, group_stride)
 
 
 def softmax_rows(S, lds, P, ldp, rows, cols, rows_per_group=0, group_stride=0, p_off=0):
-    _lib.check(_lib.load().bmhrl_softmax_rows(S.data_ptr(), lds, P.data_ptr() + 2 * p_off, ldp, rows, cols, rows_per_group,
-                                              group_stride, stream()), "bmhrl_softmax_rows")
+    _launch("bmhrl_softmax_rows", S, lds, _at(P, p_off), ldp, rows, cols, rows_per_group, group_stride)
 
 
 def attn_delta(dO, lddo, O, ldo, delta, B, H, Sq, dk, scale=1.0):
-    _lib.check(_lib.load().bmhrl_attn_delta(dO.data_ptr(), lddo, O.data_ptr(), ldo, delta.data_ptr(), scale, B, H, Sq, dk, stream()),
-               "bmhrl_attn_delta")
+    _launch("bmhrl_attn_delta", dO, lddo, O, ldo, delta, scale, B, H, Sq, dk)
 
 
 def attention_bwd_scores256_ok(Sq, Sk, dk, msq):
-    return bool(_lib.load().bmhrl_attention_bwd_scores256_ok(Sq, Sk, dk, msq))
+    return bool(_query("bmhrl_attention_bwd_scores256_ok", Sq, Sk, dk, msq))
 
 
 def attention_bwd_scores256(Q, ldq, K, ldk, V, ldv, dO, lddo, row_max, row_sum, mask, msb, P, dS, ldp, B, H, Sq, Sk, scale,
                             q_off=0, k_off=0, v_off=0):
     """P and dS (bf16 (B, H, Sq, ldp)) of a head-dimension-256 attention with at most 256 keys from the forward's statistics:
     one launch (csrc/attention_bwd256.hip); offsets in elements"""
-    _need_cuda(Q)
-    _lib.check(_lib.load().bmhrl_attention_bwd_scores256(Q.data_ptr() + 2 * q_off, ldq, K.data_ptr() + 2 * k_off, ldk,
-                                                         V.data_ptr() + 2 * v_off, ldv, dO.data_ptr(), lddo, row_max.data_ptr(),
-                                                         row_sum.data_ptr(), _p(mask), msb, P.data_ptr(), dS.data_ptr(), ldp, B, H,
-                                                         Sq, Sk, scale, stream()), "bmhrl_attention_bwd_scores256")
+    _launch("bmhrl_attention_bwd_scores256", _at(Q, q_off), ldq, _at(K, k_off), ldk, _at(V, v_off), ldv, dO, lddo, row_max,
+            row_sum, mask, msb, P, dS, ldp, B, H, Sq, Sk, scale)
 
 
 def layernorm_fwd(x, gamma, beta, y_bf16, ldy, y_f32, mean, rstd, rows, D):
-    _need_cuda(x)
-    _lib.check(_lib.load().bmhrl_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _p(y_bf16), ldy, _p(y_f32),
-                                               _p(mean), _p(rstd), rows, D, stream()), "bmhrl_layernorm_fwd")
+    _launch("bmhrl_layernorm_fwd", x, gamma, beta, y_bf16, ldy, y_f32, mean, rstd, rows, D)
 
 
 def layernorm_fwd_groups(x, gamma, beta, y_bf16, ldy, y_f32, mean, rstd, rows_per_group, D, groups):
     """`groups` LayerNorms of rows_per_group rows each, back to back, in one launch; gamma / beta are (groups, D)"""
-    _need_cuda(x)
     if gamma.numel() != groups * D or beta.numel() != groups * D:
         raise RuntimeError("layernorm_fwd_groups: gamma / beta must hold one row of D per group")
-    _lib.check(_lib.load().bmhrl_layernorm_fwd_groups(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _p(y_bf16), ldy, _p(y_f32),
-                                                      _p(mean), _p(rstd), rows_per_group, D, groups, stream()),
-               "bmhrl_layernorm_fwd_groups")
+    _launch("bmhrl_layernorm_fwd_groups", x, gamma, beta, y_bf16, ldy, y_f32, mean, rstd, rows_per_group, D, groups)
 
 
 def deterministic() -> bool:
     """BMHRL_DETERMINISTIC as the LIBRARY reads it (bmhrl_deterministic_enabled: one parse for both sides)"""
     global _DETERMINISTIC
     if _DETERMINISTIC is None:
-        _DETERMINISTIC = bool(_lib.load().bmhrl_deterministic_enabled())
+        _DETERMINISTIC = bool(_query("bmhrl_deterministic_enabled"))
     return _DETERMINISTIC
 
 
@@ -339,7 +334,6 @@ _DETERMINISTIC = None
 
 def layernorm_bwd_groups(dy, x, gamma, mean, rstd, dx, dx_add, dgamma, dbeta, rows_per_group, D, groups):
     """backward of layernorm_fwd_groups; dgamma / dbeta (groups, D) are ADDED to (zero them first)"""
-    _need_cuda(x)
     if deterministic():         # ordered parameter gradients: the two-stage form with a workspace per call, group by group
         R = rows_per_group
         for g in range(groups):
@@ -349,69 +343,51 @@ def layernorm_bwd_groups(dy, x, gamma, mean, rstd, dx, dx_add, dgamma, dbeta, ro
         return
     if gamma.numel() != groups * D or any(t is not None and t.numel() != groups * D for t in (dgamma, dbeta)):
         raise RuntimeError("layernorm_bwd_groups: gamma / dgamma / dbeta must hold one row of D per group")
-    _lib.check(_lib.load().bmhrl_layernorm_bwd_groups(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                      dx.data_ptr(), _p(dx_add), _p(dgamma), _p(dbeta), rows_per_group, D, groups,
-                                                      stream()), "bmhrl_layernorm_bwd_groups")
+    _launch("bmhrl_layernorm_bwd_groups", dy, x, gamma, mean, rstd, dx, dx_add, dgamma, dbeta, rows_per_group, D, groups)
 
 
 def layernorm_bwd_workspace(rows, D) -> int:
     """fp32 elements of the scratch the two-stage column sums of layernorm_bwd go through (uninitialised is fine)."""
-    return int(_lib.load().bmhrl_layernorm_bwd_workspace(rows, D))
+    return int(_query("bmhrl_layernorm_bwd_workspace", rows, D))
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dx_add, dgamma, dbeta, rows, D, workspace=None):
     if workspace is None:
         workspace = torch.empty(layernorm_bwd_workspace(rows, D), device=x.device)
-    _lib.check(_lib.load().bmhrl_layernorm_bwd_ws(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                  dx.data_ptr(), _p(dx_add), _p(dgamma), _p(dbeta), rows, D,
-                                                  workspace.data_ptr(), workspace.numel(), stream()),
-               "bmhrl_layernorm_bwd_ws")
+    _launch("bmhrl_layernorm_bwd_ws", dy, x, gamma, mean, rstd, dx, dx_add, dgamma, dbeta, rows, D, workspace, workspace.numel())
 
 
 def add_posenc(a, b, pe, out, out_bf16, ldob, B, S, D, dropout_p=0.0, seed=0, seed_dev=None):
-    _need_cuda(a)
-    _lib.check(_lib.load().bmhrl_add_posenc(a.data_ptr(), _p(b), pe.data_ptr(), out.data_ptr(), _p(out_bf16), ldob, B, S, D,
-                                            dropout_p, seed, _p(seed_dev), stream()), "bmhrl_add_posenc")
+    _launch("bmhrl_add_posenc", a, b, pe, out, out_bf16, ldob, B, S, D, dropout_p, seed, seed_dev)
 
 
 def embed_posenc(tok, tok2, mix, table, pe, emb_out, out, B, L, D, scale, dropout_p=0.0, seed=0, seed_dev=None):
-    _need_cuda(tok, table)
-    _lib.check(_lib.load().bmhrl_embed_posenc(tok.data_ptr(), _p(tok2), mix, table.data_ptr(), pe.data_ptr(), _p(emb_out),
-                                              out.data_ptr(), B, L, D, scale, dropout_p, seed, _p(seed_dev), stream()), "bmhrl_embed_posenc")
+    _launch("bmhrl_embed_posenc", tok, tok2, mix, table, pe, emb_out, out, B, L, D, scale, dropout_p, seed, seed_dev)
 
 
 def embed_bwd(tok, tok2, mix, dC, dtable, B, L, D, scale):
-    _lib.check(_lib.load().bmhrl_embed_bwd(tok.data_ptr(), _p(tok2), mix, dC.data_ptr(), dtable.data_ptr(), B, L, D, scale,
-                                           stream()), "bmhrl_embed_bwd")
+    _launch("bmhrl_embed_bwd", tok, tok2, mix, dC, dtable, B, L, D, scale)
 
 
 def cast_bf16(x, ldx, y, ldy, rows, cols, scale=1.0, dropout_p=0.0, seed=0, y_off=0, seed_dev=None):
-    _need_cuda(x, y)
-    _lib.check(_lib.load().bmhrl_cast_bf16(x.data_ptr(), ldx, y.data_ptr() + 2 * y_off, ldy, rows, cols, scale, dropout_p,
-                                           seed, _p(seed_dev), stream()), "bmhrl_cast_bf16")
+    _launch("bmhrl_cast_bf16", x, ldx, _at(y, y_off), ldy, rows, cols, scale, dropout_p, seed, seed_dev)
 
 
 def cast_split3_bf16(x, ldx, y, ldy, part, lo_slot, rows, cols, y_off=0, x2=None, ldx2=0, cols2=0):
     """y blocks [hi | . | .] of width `part`: bf16(x) in block 0, bf16(x - hi) in block lo_slot, hi again in the other;
     x2 (rows, cols2): a second source whose columns follow x's inside every block"""
-    _need_cuda(x, y)
-    _lib.check(_lib.load().bmhrl_cast_split3_bf16(x.data_ptr(), ldx, y.data_ptr() + 2 * y_off, ldy, part, lo_slot, rows, cols,
-                                                  _p(x2), ldx2, cols2, stream()), "bmhrl_cast_split3_bf16")
+    _launch("bmhrl_cast_split3_bf16", x, ldx, _at(y, y_off), ldy, part, lo_slot, rows, cols, x2, ldx2, cols2)
 
 
 def cast_colsum_bf16(x, ldx, y, ldy, rows, cols, colsum, scale=1.0, dropout_p=0.0, seed=0, seed_dev=None, colsum_off=0,
                      group_rows=None, colsum_stride=0):
     """y = bf16(x * scale * dropout); colsum[colsum_off + n] += column sums of y (colsum must start zeroed).
     group_rows: the rows form groups of that many, group g adds into colsum[colsum_off + g * colsum_stride + n]"""
-    _need_cuda(x, y, colsum)
     if group_rows is not None:
-        _lib.check(_lib.load().bmhrl_cast_colsum_bf16_groups(x.data_ptr(), ldx, y.data_ptr(), ldy, rows, cols, scale, dropout_p,
-                                                             seed, _p(seed_dev), colsum.data_ptr() + 4 * colsum_off, group_rows,
-                                                             colsum_stride, stream()), "bmhrl_cast_colsum_bf16_groups")
+        _launch("bmhrl_cast_colsum_bf16_groups", x, ldx, y, ldy, rows, cols, scale, dropout_p, seed, seed_dev,
+                _at(colsum, colsum_off), group_rows, colsum_stride)
         return
-    _lib.check(_lib.load().bmhrl_cast_colsum_bf16(x.data_ptr(), ldx, y.data_ptr(), ldy, rows, cols, scale, dropout_p, seed,
-                                                  _p(seed_dev), colsum.data_ptr() + 4 * colsum_off, stream()),
-               "bmhrl_cast_colsum_bf16")
+    _launch("bmhrl_cast_colsum_bf16", x, ldx, y, ldy, rows, cols, scale, dropout_p, seed, seed_dev, _at(colsum, colsum_off))
 
 
 SEG_ELEMS_PER_BLOCK = 4096
@@ -419,97 +395,80 @@ SEG_ELEMS_PER_BLOCK = 4096
 
 def cast_segments(table: torch.Tensor, n_segments: int, n_blocks: int):
     """table: int64 (n_segments, 6) on the device -- see bmhrl_cast_segments in include/bmhrl_hip.h"""
-    _need_cuda(table)
-    _lib.check(_lib.load().bmhrl_cast_segments(table.data_ptr(), n_segments, n_blocks, stream()), "bmhrl_cast_segments")
+    _launch("bmhrl_cast_segments", table, n_segments, n_blocks)
 
 
 def colsum_bf16(dY, ld, db, accumulate, rows, cols, dy_off=0, db_off=0):
-    _lib.check(_lib.load().bmhrl_colsum_bf16(dY.data_ptr() + 2 * dy_off, ld, db.data_ptr() + 4 * db_off, int(accumulate),
-                                             rows, cols, stream()), "bmhrl_colsum_bf16")
+    _launch("bmhrl_colsum_bf16", _at(dY, dy_off), ld, _at(db, db_off), int(accumulate), rows, cols)
 
 
 def colsum_bf16_groups(dY, ld, db, rows_per_group, cols, groups, db_stride):
     """db[g * db_stride + n] += sum over the rows of group g of dY[., n] (bf16 (groups * rows_per_group, ld)); one launch"""
-    _lib.check(_lib.load().bmhrl_colsum_bf16_groups(dY.data_ptr(), ld, db.data_ptr(), rows_per_group, cols, groups, db_stride,
-                                                    stream()), "bmhrl_colsum_bf16_groups")
+    _launch("bmhrl_colsum_bf16_groups", dY, ld, db, rows_per_group, cols, groups, db_stride)
 
 
 def cast_bf16_copies(x, ldx, y, ldy, rows, cols, copies, copy_stride):
     """y[c * copy_stride + r * ldy + n] = bf16(x[r * ldx + n]) for every copy c; one launch"""
-    _need_cuda(x, y)
-    _lib.check(_lib.load().bmhrl_cast_bf16_copies(x.data_ptr(), ldx, y.data_ptr(), ldy, rows, cols, copies, copy_stride, stream()),
-               "bmhrl_cast_bf16_copies")
+    _launch("bmhrl_cast_bf16_copies", x, ldx, y, ldy, rows, cols, copies, copy_stride)
 
 
 def gate_fwd(cv, ca, a_v, out, out_bf16, ldob, rows, D):
-    _lib.check(_lib.load().bmhrl_gate_fwd(cv.data_ptr(), ca.data_ptr(), a_v.data_ptr(), out.data_ptr(), _p(out_bf16), ldob,
-                                          rows, D, stream()), "bmhrl_gate_fwd")
+    _launch("bmhrl_gate_fwd", cv, ca, a_v, out, out_bf16, ldob, rows, D)
 
 
 def gate_bwd(dout, cv, ca, a_v, dcv, dca, da_v, rows, D):
-    _lib.check(_lib.load().bmhrl_gate_bwd(dout.data_ptr(), cv.data_ptr(), ca.data_ptr(), a_v.data_ptr(), dcv.data_ptr(),
-                                          dca.data_ptr(), _p(da_v), rows, D, stream()), "bmhrl_gate_bwd")
+    _launch("bmhrl_gate_bwd", dout, cv, ca, a_v, dcv, dca, da_v, rows, D)
 
 
 def _tail_groups(groups, grads=None):
     arr = (_lib.FusionTailParams * len(groups))()
     for i, (g, a) in enumerate(zip(groups, arr)):
-        a.gamma_ca, a.beta_ca, a.gamma_cv, a.beta_cv, a.a_v = (t.data_ptr() for t in g)
+        a.gamma_ca, a.beta_ca, a.gamma_cv, a.beta_cv, a.a_v = map(_ptr, g)
         if grads is not None:
-            a.dgamma_ca, a.dbeta_ca, a.dgamma_cv, a.dbeta_cv, a.da_v = (_p(t) for t in grads[i])
+            a.dgamma_ca, a.dbeta_ca, a.dgamma_cv, a.dbeta_cv, a.da_v = map(_ptr, grads[i])
     return arr
 
 
 def fusion_tail_fwd(ca, cv, groups, rows_per_group, D, out, stats, out_bf16=None, ldob=0):
     """out = g * LN_CV(cv) + (1 - g) * LN_CA(ca); groups: list (1 or 2) of (gamma_ca, beta_ca, gamma_cv, beta_cv, a_v);
     out_bf16 (rows, ldob): the same values in bf16 as well"""
-    _need_cuda(ca, cv, out, stats)
     arr = _tail_groups(groups)
-    _lib.check(_lib.load().bmhrl_fusion_tail_fwd(ca.data_ptr(), cv.data_ptr(), C.cast(arr, C.c_void_p), len(groups), rows_per_group, D,
-                                                 out.data_ptr(), stats.data_ptr(), _p(out_bf16), ldob, stream()), "bmhrl_fusion_tail_fwd")
+    _launch("bmhrl_fusion_tail_fwd", ca, cv, C.cast(arr, C.c_void_p), len(groups), rows_per_group, D, out, stats, out_bf16, ldob)
 
 
 def fusion_tail_bwd(dout, ca, cv, stats, groups, grads, rows_per_group, D, dca, dcv, dout1=None, ldd0=0, ldd1=0):
     """grads: per group (dgamma_ca, dbeta_ca, dgamma_cv, dbeta_cv, da_v), zeroed fp32 tensors or None.
     dout: gradient of group 0's rows (row stride ldd0, 0 = D); dout1: of group 1's (None: behind group 0's in dout)"""
-    _need_cuda(dout, ca, cv, stats, dca, dcv)
     arr = _tail_groups(groups, grads)
-    _lib.check(_lib.load().bmhrl_fusion_tail_bwd(dout.data_ptr(), _p(dout1), ldd0, ldd1, ca.data_ptr(), cv.data_ptr(), stats.data_ptr(),
-                                                 C.cast(arr, C.c_void_p), len(groups), rows_per_group, D, dca.data_ptr(),
-                                                 dcv.data_ptr(), stream()), "bmhrl_fusion_tail_bwd")
+    _launch("bmhrl_fusion_tail_bwd", dout, dout1, ldd0, ldd1, ca, cv, stats, C.cast(arr, C.c_void_p), len(groups), rows_per_group,
+            D, dca, dcv)
 
 
 def expand_goals_index(seg, src, B, L):
-    _lib.check(_lib.load().bmhrl_expand_goals_index(seg.data_ptr(), src.data_ptr(), B, L, stream()), "bmhrl_expand_goals_index")
+    _launch("bmhrl_expand_goals_index", seg, src, B, L)
 
 
 def expand_goals(seg, x, src, out, out_bf16, ldob, B, L, D):
     """row map of Manager.expand_goals from the int32 labels `seg` (B, L) + the gather along it, one launch"""
-    _need_cuda(seg, x, src, out)
-    _lib.check(_lib.load().bmhrl_expand_goals(seg.data_ptr(), x.data_ptr(), src.data_ptr(), out.data_ptr(), _p(out_bf16), ldob,
-                                              B, L, D, stream()), "bmhrl_expand_goals")
+    _launch("bmhrl_expand_goals", seg, x, src, out, out_bf16, ldob, B, L, D)
 
 
 def expand_goals_explore(seg, x, src, out, out_bf16, ldob, B, L, D, mean_factor, std_factor, seed, seed_dev=None, noise_out=None):
     """expand_goals with the manager's exploration vector (reference :444-452) added in the same launch"""
-    _need_cuda(seg, x, src, out)
-    _lib.check(_lib.load().bmhrl_expand_goals_explore(seg.data_ptr(), x.data_ptr(), src.data_ptr(), out.data_ptr(), _p(out_bf16),
-                                                      ldob, B, L, D, float(mean_factor), float(std_factor), int(seed),
-                                                      _p(seed_dev), _p(noise_out), stream()), "bmhrl_expand_goals_explore")
+    _launch("bmhrl_expand_goals_explore", seg, x, src, out, out_bf16, ldob, B, L, D, float(mean_factor), float(std_factor),
+            int(seed), seed_dev, noise_out)
 
 
 def gather_rows(x, src, out, out_bf16, ldob, rows, D):
-    _lib.check(_lib.load().bmhrl_gather_rows(x.data_ptr(), src.data_ptr(), out.data_ptr(), _p(out_bf16), ldob, rows, D,
-                                             stream()), "bmhrl_gather_rows")
+    _launch("bmhrl_gather_rows", x, src, out, out_bf16, ldob, rows, D)
 
 
 def scatter_add_rows(dout, src, dx, rows, D):
-    _lib.check(_lib.load().bmhrl_scatter_add_rows(dout.data_ptr(), src.data_ptr(), dx.data_ptr(), rows, D, stream()),
-               "bmhrl_scatter_add_rows")
+    _launch("bmhrl_scatter_add_rows", dout, src, dx, rows, D)
 
 
 def log_softmax_(logits, ld, rows, V):
-    _lib.check(_lib.load().bmhrl_log_softmax(logits.data_ptr(), ld, rows, V, stream()), "bmhrl_log_softmax")
+    _launch("bmhrl_log_softmax", logits, ld, rows, V)
 
 
 def _amp_form(what, biased_trg, n_row, amp_given):
@@ -523,41 +482,33 @@ def _amp_form(what, biased_trg, n_row, amp_given):
 def smooth_kl_fwd(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, row_loss, amp_out, rows, V,
                   amp_given=False):
     _amp_form("smooth_kl_fwd", biased_trg, n_row, amp_given)
-    _lib.check(_lib.load().bmhrl_smooth_kl_fwd(logp.data_ptr(), ld, trg.data_ptr(), _p(biased_trg), _p(score), _p(n_row),
-                                               smoothing, pad_idx, zero_pad_rows, row_loss.data_ptr(), _p(amp_out), rows, V,
-                                               stream()), "bmhrl_smooth_kl_fwd")
+    _launch("bmhrl_smooth_kl_fwd", logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, row_loss, amp_out,
+            rows, V)
 
 
 def smooth_kl_full(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, out, rows, V, amp_given=False):
     """the unreduced (rows, V) divergence of LabelSmoothing / BiasedKL (no gradient: the differentiable form is the row sums)"""
     _amp_form("smooth_kl_full", biased_trg, n_row, amp_given)
-    _need_cuda(logp, out)
-    _lib.check(_lib.load().bmhrl_smooth_kl_full(logp.data_ptr(), ld, trg.data_ptr(), _p(biased_trg), _p(score), _p(n_row), smoothing,
-                                                pad_idx, zero_pad_rows, out.data_ptr(), rows, V, stream()), "bmhrl_smooth_kl_full")
+    _launch("bmhrl_smooth_kl_full", logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, out, rows, V)
 
 
 def smooth_kl_bwd(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, loss_scale, g_bf16, ldg,
                   g_f32, rows, V, wrt_logits=True, loss_scale2=None, amp_given=False):
     """loss_scale (and the optional loss_scale2, multiplied in) are one-element device tensors"""
     _amp_form("smooth_kl_bwd", biased_trg, n_row, amp_given)
-    _lib.check(_lib.load().bmhrl_smooth_kl_bwd(logp.data_ptr(), ld, trg.data_ptr(), _p(biased_trg), _p(score), _p(n_row),
-                                               smoothing, pad_idx, zero_pad_rows, loss_scale.data_ptr(), _p(loss_scale2),
-                                               int(wrt_logits), _p(g_bf16), ldg, _p(g_f32), rows, V, stream()), "bmhrl_smooth_kl_bwd")
+    _launch("bmhrl_smooth_kl_bwd", logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, loss_scale,
+            loss_scale2, int(wrt_logits), g_bf16, ldg, g_f32, rows, V)
 
 
 def smooth_kl_amp_grad(logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, out, rows, V, amp_given=False):
     """d rows / d log(raw amplitude); amp_given (n_row None): `score` is the amplitude itself and the result is d rows / d amplitude"""
     _amp_form("smooth_kl_amp_grad", biased_trg, n_row, amp_given)
-    _lib.check(_lib.load().bmhrl_smooth_kl_amp_grad(logp.data_ptr(), ld, trg.data_ptr(), biased_trg.data_ptr(), score.data_ptr(),
-                                                    _p(n_row), smoothing, pad_idx, zero_pad_rows, out.data_ptr(), rows, V,
-                                                    stream()), "bmhrl_smooth_kl_amp_grad")
+    _launch("bmhrl_smooth_kl_amp_grad", logp, ld, trg, biased_trg, score, n_row, smoothing, pad_idx, zero_pad_rows, out, rows, V)
 
 
 def token_loss_reduce(row_loss, trg, rows, pad_idx, weight, factor, loss, scale):
     """loss = weight * sum(row_loss) / (#(trg != pad) * factor); scale = weight / (#tokens * factor) (device scalars)"""
-    _need_cuda(row_loss, trg, loss, scale)
-    _lib.check(_lib.load().bmhrl_token_loss_reduce(row_loss.data_ptr(), trg.data_ptr(), rows, pad_idx, _p(weight), factor,
-                                                   loss.data_ptr(), scale.data_ptr(), stream()), "bmhrl_token_loss_reduce")
+    _launch("bmhrl_token_loss_reduce", row_loss, trg, rows, pad_idx, weight, factor, loss, scale)
 
 
 def head_loss_ok(V, ld, ldg):
@@ -567,36 +518,27 @@ def head_loss_ok(V, ld, ldg):
 def head_loss(logits, ld, trg, smoothing, pad_idx, weight, factor, dloss, row_loss, loss_scale, g_bf16, ldg, counter, rows, V):
     """log-softmax in place + label-smoothing row sums + the loops' token-normalised loss (loss_scale = [loss, scale]) + bf16
     d logits for the incoming gradient `dloss` (device scalar or None = 1), one launch"""
-    _need_cuda(logits, trg, row_loss, loss_scale, g_bf16, counter)
-    _lib.check(_lib.load().bmhrl_head_loss(logits.data_ptr(), ld, trg.data_ptr(), smoothing, pad_idx, _p(weight), factor, _p(dloss),
-                                           row_loss.data_ptr(), loss_scale.data_ptr(), g_bf16.data_ptr(), ldg, counter.data_ptr(),
-                                           rows, V, stream()), "bmhrl_head_loss")
+    _launch("bmhrl_head_loss", logits, ld, trg, smoothing, pad_idx, weight, factor, dloss, row_loss, loss_scale, g_bf16, ldg,
+            counter, rows, V)
 
 
 def log_softmax_bwd(dlogp, logp, ld, g_bf16, ldg, rows, V):
-    _lib.check(_lib.load().bmhrl_log_softmax_bwd(dlogp.data_ptr(), logp.data_ptr(), ld, g_bf16.data_ptr(), ldg, rows, V, stream()),
-               "bmhrl_log_softmax_bwd")
+    _launch("bmhrl_log_softmax_bwd", dlogp, logp, ld, g_bf16, ldg, rows, V)
 
 
 def sample_tokens(logp, ld, out, p_out, rows, V, greedy, seed, seed_dev=None, row_offset=0):
     """one token per row, inverse-CDF sample for uniform01(seed + seed_dev[0], row + row_offset) or (greedy) the first maximum;
     p_out = exp(logp[token]).  The token is always in [0, V): a row in which no entry exceeds -inf (all NaN, all -inf) gives
     token 0 under greedy, and its p_out = exp(logp[row, 0]) still shows the NaN."""
-    _lib.check(_lib.load().bmhrl_sample_tokens(logp.data_ptr(), ld, out.data_ptr(), _p(p_out), rows, V, int(greedy), seed,
-                                               _p(seed_dev), row_offset, stream()), "bmhrl_sample_tokens")
+    _launch("bmhrl_sample_tokens", logp, ld, out, p_out, rows, V, int(greedy), seed, seed_dev, row_offset)
 
 
 def reinforce_fwd(pred, ld, action, value, critic_value, row_policy, row_value, rows, V, is_logp=True):
-    _need_cuda(pred)
-    _lib.check(_lib.load().bmhrl_reinforce_fwd(pred.data_ptr(), ld, int(is_logp), action.data_ptr(), value.data_ptr(),
-                                               critic_value.data_ptr(), row_policy.data_ptr(), row_value.data_ptr(), rows, V,
-                                               stream()), "bmhrl_reinforce_fwd")
+    _launch("bmhrl_reinforce_fwd", pred, ld, int(is_logp), action, value, critic_value, row_policy, row_value, rows, V)
 
 
 def reinforce_bwd(probs, ld, action, value, critic_value, gscale, dprobs, dvalue, dcritic, rows, V):
-    _lib.check(_lib.load().bmhrl_reinforce_bwd(probs.data_ptr(), ld, action.data_ptr(), value.data_ptr(),
-                                               critic_value.data_ptr(), gscale.data_ptr(), dprobs.data_ptr(), _p(dvalue),
-                                               _p(dcritic), rows, V, stream()), "bmhrl_reinforce_bwd")
+    _launch("bmhrl_reinforce_bwd", probs, ld, action, value, critic_value, gscale, dprobs, dvalue, dcritic, rows, V)
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, step_dev=None,
@@ -604,42 +546,31 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight
     """hyper: the optimizer's hyper-parameter block (include/bmhrl_hip.h) -- the learning rate and the clip coefficient are
     read from it on the device (bmhrl_adam_step_dev) and `lr` is not used"""
     if hyper is not None:
-        _need_cuda(param, hyper)
-        _lib.check(_lib.load().bmhrl_adam_step_dev(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
-                                                   lr, beta1, beta2, eps, weight_decay, step, _p(step_dev), grad_scale,
-                                                   hyper.data_ptr(), stream()), "bmhrl_adam_step_dev")
+        _launch("bmhrl_adam_step_dev", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, step_dev,
+                grad_scale, hyper)
         return
-    _lib.check(_lib.load().bmhrl_adam_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n, lr,
-                                           beta1, beta2, eps, weight_decay, step, _p(step_dev), grad_scale, stream()), "bmhrl_adam_step")
+    _launch("bmhrl_adam_step", param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, step_dev, grad_scale)
 
 
 def grad_norm(table, n_segments, n_blocks, grad, grad_scale, partials, hyper):
     """hyper[3] = L2 norm of the gradient the Adam table describes (x grad_scale), hyper[2] = the clip coefficient for the
     threshold in hyper[1] (bmhrl_grad_norm in include/bmhrl_hip.h); partials: fp32 workspace, one element per block"""
-    _need_cuda(table, grad, partials, hyper)
-    _lib.check(_lib.load().bmhrl_grad_norm(table.data_ptr(), n_segments, n_blocks, grad.data_ptr(), grad_scale,
-                                           partials.data_ptr(), partials.numel(), hyper.data_ptr(), stream()), "bmhrl_grad_norm")
+    _launch("bmhrl_grad_norm", table, n_segments, n_blocks, grad, grad_scale, partials, partials.numel(), hyper)
 
 
 def accum_segments(table, n_segments, n_blocks, grad, accum, ctl, loss_in=None, loss_out=None):
     """accum = w * g (ctl[1] != 0: the first micro-batch of a window, a store) or fma(w, g, accum), w = ctl[0], over the
     gradient the Adam table describes (bmhrl_accum_segments in include/bmhrl_hip.h); ctl: two fp32 device words;
     loss_in / loss_out: optional fp32 device scalars, loss_out = (first ? 0 : loss_out) + w * loss_in in the same launch"""
-    _need_cuda(table, grad, accum, ctl, loss_in, loss_out)
-    _lib.check(_lib.load().bmhrl_accum_segments(table.data_ptr(), n_segments, n_blocks, grad.data_ptr(), accum.data_ptr(),
-                                                ctl.data_ptr(), _p(loss_in), _p(loss_out), stream()), "bmhrl_accum_segments")
+    _launch("bmhrl_accum_segments", table, n_segments, n_blocks, grad, accum, ctl, loss_in, loss_out)
 
 
 def gemm_f32(A, W, bias1, bias2, C, M, N, K):
-    _need_cuda(A, W, C)
-    _lib.check(_lib.load().bmhrl_gemm_f32(A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), _p(bias1), _p(bias2),
-                                          C.data_ptr(), C.stride(0), M, N, K, stream()), "bmhrl_gemm_f32")
+    _launch("bmhrl_gemm_f32", A, A.stride(0), W, W.stride(0), bias1, bias2, C, C.stride(0), M, N, K)
 
 
 def rnn_step(gates, xproj, whh, bhh, h_prev, c_prev, h_out, c_out, seq_out, ar_alpha, ar_beta, B, L, H, t):
-    _lib.check(_lib.load().bmhrl_rnn_step(gates, xproj.data_ptr(), whh.data_ptr(), _p(bhh), _p(h_prev), _p(c_prev),
-                                          h_out.data_ptr(), _p(c_out), seq_out.data_ptr(), _p(ar_alpha), _p(ar_beta), B, L, H, t,
-                                          stream()), "bmhrl_rnn_step")
+    _launch("bmhrl_rnn_step", gates, xproj, whh, bhh, h_prev, c_prev, h_out, c_out, seq_out, ar_alpha, ar_beta, B, L, H, t)
 
 
 def rnn_wavefront(layers, B, L, H, chunk=1):
@@ -647,86 +578,69 @@ def rnn_wavefront(layers, B, L, H, chunk=1):
     L + chunk * (len(layers) - 1) launches"""
     arr = (_lib.RnnLayer * len(layers))()
     for d, a in zip(layers, arr):
-        a.w_ih, a.w_hh, a.b_ih, a.b_hh = d["w_ih"].data_ptr(), d["w_hh"].data_ptr(), d["b_ih"].data_ptr(), d["b_hh"].data_ptr()
-        a.in_seq, a.in_ld, a.in_dim, a.gates = d["in_seq"].data_ptr(), d["in_ld"], d["in_dim"], d["gates"]
-        a.seq_out = d["seq_out"].data_ptr()
-        a.h[0], a.h[1] = d["h"][0].data_ptr(), d["h"][1].data_ptr()
-        a.c[0], a.c[1] = (d["c"][0].data_ptr(), d["c"][1].data_ptr()) if d.get("c") is not None else (None, None)
-        a.arelu_alpha, a.arelu_beta = _p(d.get("arelu_alpha")), _p(d.get("arelu_beta"))
-        a.xproj = _p(d.get("xproj"))
-    _lib.check(_lib.load().bmhrl_rnn_wavefront(C.cast(arr, C.c_void_p), len(layers), B, L, H, chunk, stream()),
-               "bmhrl_rnn_wavefront")
+        a.w_ih, a.w_hh, a.b_ih, a.b_hh = _ptr(d["w_ih"]), _ptr(d["w_hh"]), _ptr(d["b_ih"]), _ptr(d["b_hh"])
+        a.in_seq, a.in_ld, a.in_dim, a.gates = _ptr(d["in_seq"]), d["in_ld"], d["in_dim"], d["gates"]
+        a.seq_out = _ptr(d["seq_out"])
+        a.h[0], a.h[1] = _ptr(d["h"][0]), _ptr(d["h"][1])
+        a.c[0], a.c[1] = (_ptr(d["c"][0]), _ptr(d["c"][1])) if d.get("c") is not None else (None, None)
+        a.arelu_alpha, a.arelu_beta = _ptr(d.get("arelu_alpha")), _ptr(d.get("arelu_beta"))
+        a.xproj = _ptr(d.get("xproj"))
+    _launch("bmhrl_rnn_wavefront", C.cast(arr, C.c_void_p), len(layers), B, L, H, chunk)
 
 
 def critic_head(x, w, b, threshold, score, labels, rows, H):
-    _lib.check(_lib.load().bmhrl_critic_head(x.data_ptr(), w.data_ptr(), b.data_ptr(), threshold, _p(score), _p(labels), rows, H,
-                                             stream()), "bmhrl_critic_head")
+    _launch("bmhrl_critic_head", x, w, b, threshold, score, labels, rows, H)
 
 
 def rnn_step_train(gates, xproj, whh, bhh, h_seq, hprev_seq, c_seq, gate_seq, hn_seq, y_seq, ar_alpha, ar_beta, B, L, H, t):
     """one training-forward time step of one layer (bmhrl_rnn_step_train): rnn_step that keeps what the backward needs"""
-    _need_cuda(xproj, whh, bhh, h_seq, hprev_seq, c_seq, gate_seq, hn_seq, y_seq, ar_alpha, ar_beta)
-    _lib.check(_lib.load().bmhrl_rnn_step_train(gates, _p(xproj), _p(whh), _p(bhh), _p(h_seq), _p(hprev_seq), _p(c_seq), _p(gate_seq), _p(hn_seq),
-                                                _p(y_seq), _p(ar_alpha), _p(ar_beta), B, L, H, t, stream()), "bmhrl_rnn_step_train")
+    _launch("bmhrl_rnn_step_train", gates, xproj, whh, bhh, h_seq, hprev_seq, c_seq, gate_seq, hn_seq, y_seq, ar_alpha, ar_beta,
+            B, L, H, t)
 
 
 def rnn_bwd_step(gates, whh, dy, h_seq, c_seq, gate_seq, hn_seq, carry, dax, dah, ar_alpha, ar_beta, B, L, H, t):
     """backward of one cell, t descending (bmhrl_rnn_bwd_step); the LSTM passes dah=None"""
-    _need_cuda(whh, dy, h_seq, c_seq, gate_seq, hn_seq, carry, dax, dah, ar_alpha, ar_beta)
-    _lib.check(_lib.load().bmhrl_rnn_bwd_step(gates, _p(whh), _p(dy), _p(h_seq), _p(c_seq), _p(gate_seq), _p(hn_seq), _p(carry),
-                                              _p(dax), _p(dah), _p(ar_alpha), _p(ar_beta), B, L, H, t, stream()), "bmhrl_rnn_bwd_step")
+    _launch("bmhrl_rnn_bwd_step", gates, whh, dy, h_seq, c_seq, gate_seq, hn_seq, carry, dax, dah, ar_alpha, ar_beta, B, L, H, t)
 
 
 def gemm_f32_nn(A, Bm, C, M, N, K, a_kmajor=False):
     """C[M,N] = op(A) . B, B (K, N) row-major; A (M, K) row-major or, a_kmajor, (K, M) row-major (bmhrl_gemm_f32_nn)"""
-    _need_cuda(A, Bm, C)
-    _lib.check(_lib.load().bmhrl_gemm_f32_nn(_p(A), 0 if A is None else A.stride(0), int(a_kmajor), _p(Bm),
-                                             0 if Bm is None else Bm.stride(0), _p(C), 0 if C is None else C.stride(0), M, N, K,
-                                             stream()), "bmhrl_gemm_f32_nn")
+    _launch("bmhrl_gemm_f32_nn", A, 0 if A is None else A.stride(0), int(a_kmajor), Bm, 0 if Bm is None else Bm.stride(0), C,
+            0 if C is None else C.stride(0), M, N, K)
 
 
 def rnn_bias_grad(dax, dah, db_x, db_h, rows, N):
-    _need_cuda(dax, dah, db_x, db_h)
-    _lib.check(_lib.load().bmhrl_rnn_bias_grad(_p(dax), _p(dah), _p(db_x), _p(db_h), rows, N, stream()), "bmhrl_rnn_bias_grad")
+    _launch("bmhrl_rnn_bias_grad", dax, dah, db_x, db_h, rows, N)
 
 
 def arelu_grad(dy, h, alpha, beta, dalpha, dbeta, n):
     """ordered AReLU parameter gradients over n elements (bmhrl_arelu_grad)"""
-    _need_cuda(dy, h, alpha, beta, dalpha, dbeta)
     partial = None if dy is None else torch.empty(128, device=dy.device)
-    _lib.check(_lib.load().bmhrl_arelu_grad(_p(dy), _p(h), _p(alpha), _p(beta), _p(partial), _p(dalpha), _p(dbeta), n, stream()),
-               "bmhrl_arelu_grad")
+    _launch("bmhrl_arelu_grad", dy, h, alpha, beta, partial, dalpha, dbeta, n)
 
 
 def critic_head_loss(y2, lin_w, lin_b, labels, mask, pos_weight, ds_in, score, loss, ds, dy2, dlin_w, dlin_b, rows, H):
     """head (+ masked BCE-with-logits when labels is given) and its backward in one launch (bmhrl_critic_head_loss);
     mask: bool / uint8, one byte per row"""
-    _need_cuda(y2, lin_w, lin_b, labels, mask, ds_in, score, loss, ds, dy2, dlin_w, dlin_b)
-    _lib.check(_lib.load().bmhrl_critic_head_loss(_p(y2), _p(lin_w), _p(lin_b), _p(labels), _p(mask), float(pos_weight), _p(ds_in),
-                                                  _p(score), _p(loss), _p(ds), _p(dy2), _p(dlin_w), _p(dlin_b), rows, H, stream()),
-               "bmhrl_critic_head_loss")
+    _launch("bmhrl_critic_head_loss", y2, lin_w, lin_b, labels, mask, float(pos_weight), ds_in, score, loss, ds, dy2, dlin_w,
+            dlin_b, rows, H)
 
 
 def adam_segments(table, n_segments, n_blocks, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step,
                   grad_scale=1.0, step_dev=None, hyper=None):
     """Adam over the flat bucket through a per-parameter table that also names each weight's bf16 shadow (see
     bmhrl_adam_segments in include/bmhrl_hip.h); hyper: as adam_step (bmhrl_adam_segments_dev)"""
-    _need_cuda(table, param, hyper)
     if hyper is not None:
-        _lib.check(_lib.load().bmhrl_adam_segments_dev(table.data_ptr(), n_segments, n_blocks, param.data_ptr(), grad.data_ptr(),
-                                                       exp_avg.data_ptr(), exp_avg_sq.data_ptr(), lr, beta1, beta2, eps,
-                                                       weight_decay, step, _p(step_dev), grad_scale, hyper.data_ptr(), stream()),
-                   "bmhrl_adam_segments_dev")
+        _launch("bmhrl_adam_segments_dev", table, n_segments, n_blocks, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
+                weight_decay, step, step_dev, grad_scale, hyper)
         return
-    _lib.check(_lib.load().bmhrl_adam_segments(table.data_ptr(), n_segments, n_blocks, param.data_ptr(), grad.data_ptr(),
-                                               exp_avg.data_ptr(), exp_avg_sq.data_ptr(), lr, beta1, beta2, eps, weight_decay,
-                                               step, _p(step_dev), grad_scale, stream()), "bmhrl_adam_segments")
+    _launch("bmhrl_adam_segments", table, n_segments, n_blocks, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
+            weight_decay, step, step_dev, grad_scale)
 
 
 def make_masks(rgb, audio, trg, pad_idx, copies=1):
     """V_mask (copies*B, 1, Tv), A_mask (copies*B, 1, Ta), C_mask (copies*B, L, L) as bool tensors, one launch
     (model/masking.py:18-55, bimodal case; copies > 1: the same masks laid out that many times)"""
-    _need_cuda(rgb, audio, trg)
     B, Tv = rgb.shape[:2]
     Ta, L = audio.shape[1], trg.shape[1]
     if rgb.stride(2) != 1 or rgb.stride(0) != Tv * rgb.stride(1) or audio.stride(2) != 1 or audio.stride(0) != Ta * audio.stride(1):
@@ -735,9 +649,7 @@ def make_masks(rgb, audio, trg, pad_idx, copies=1):
     vm = torch.empty(copies * B, 1, Tv, dtype=torch.bool, device=rgb.device)
     am = torch.empty(copies * B, 1, Ta, dtype=torch.bool, device=rgb.device)
     cm = torch.empty(copies * B, L, L, dtype=torch.bool, device=rgb.device)
-    _lib.check(_lib.load().bmhrl_make_masks(rgb.data_ptr(), rgb.stride(1), audio.data_ptr(), audio.stride(1), trg.data_ptr(), B, Tv,
-                                            Ta, L, pad_idx, copies, vm.data_ptr(), am.data_ptr(), cm.data_ptr(), stream()),
-               "bmhrl_make_masks")
+    _launch("bmhrl_make_masks", rgb, rgb.stride(1), audio, audio.stride(1), trg, B, Tv, Ta, L, pad_idx, copies, vm, am, cm)
     return vm, am, cm
 
 
@@ -745,7 +657,6 @@ def batch_head(rgb, audio, captions, pad_idx, copies=1, bump64=None, bump32=()):
     """Head of a training step, one launch: captions (B, L + 1) -> (trg_in, trg_y) = (captions[:, :-1], captions[:, 1:])
     as contiguous tensors, make_masks() of trg_in, and `bump64` (int64 device word: the seed) / up to two int32 device
     counters in `bump32` (Adam steps) advanced by one.  Returns (vm, am, cm, trg_in, trg_y)."""
-    _need_cuda(rgb, audio, captions)
     B, Tv = rgb.shape[:2]
     Ta, L = audio.shape[1], captions.shape[1] - 1
     if rgb.stride(2) != 1 or rgb.stride(0) != Tv * rgb.stride(1) or audio.stride(2) != 1 or audio.stride(0) != Ta * audio.stride(1):
@@ -761,36 +672,28 @@ def batch_head(rgb, audio, captions, pad_idx, copies=1, bump64=None, bump32=()):
     trg_in = torch.empty(B, L, dtype=torch.int64, device=dev)
     trg_y = torch.empty(B, L, dtype=torch.int64, device=dev)
     b32 = list(bump32) + [None, None]
-    _lib.check(_lib.load().bmhrl_batch_head(rgb.data_ptr(), rgb.stride(1), audio.data_ptr(), audio.stride(1), captions.data_ptr(),
-                                            captions.stride(0), B, Tv, Ta, L, pad_idx, copies, vm.data_ptr(), am.data_ptr(),
-                                            cm.data_ptr(), trg_in.data_ptr(), trg_y.data_ptr(), _p(bump64), _p(b32[0]), _p(b32[1]),
-                                            stream()), "bmhrl_batch_head")
+    _launch("bmhrl_batch_head", rgb, rgb.stride(1), audio, audio.stride(1), captions, captions.stride(0), B, Tv, Ta, L, pad_idx,
+            copies, vm, am, cm, trg_in, trg_y, bump64, b32[0], b32[1])
     return vm, am, cm, trg_in, trg_y
 
 
 # ---- Conv1d('same') + GroupNorm input projection of the DETR-mode agent (csrc/conv_gn.hip)
 def unfold1d_bf16(x, out, ldo, B, T, C, k, left):
     """out[(b, t)][j * C + c] = x[b][t + j - left][c] (0 outside the clip), bf16: the operand of a Conv1d as a GEMM"""
-    _need_cuda(x, out)
-    _lib.check(_lib.load().bmhrl_unfold1d_bf16(x.data_ptr(), out.data_ptr(), ldo, B, T, C, k, left, stream()), "bmhrl_unfold1d_bf16")
+    _launch("bmhrl_unfold1d_bf16", x, out, ldo, B, T, C, k, left)
 
 
 def fold1d(du, ldu, dx, B, T, C, k, left):
     """dx[b][t][c] = sum_j du[(b, t - j + left)][j * C + c]: the data gradient of the unfolded operand"""
-    _need_cuda(du, dx)
-    _lib.check(_lib.load().bmhrl_fold1d(du.data_ptr(), ldu, dx.data_ptr(), B, T, C, k, left, stream()), "bmhrl_fold1d")
+    _launch("bmhrl_fold1d", du, ldu, dx, B, T, C, k, left)
 
 
 def groupnorm_fwd(x, gamma, beta, y, mean, rstd, B, T, C, G, eps):
-    _need_cuda(x, y)
-    _lib.check(_lib.load().bmhrl_groupnorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(),
-                                               rstd.data_ptr(), B, T, C, G, float(eps), stream()), "bmhrl_groupnorm_fwd")
+    _launch("bmhrl_groupnorm_fwd", x, gamma, beta, y, mean, rstd, B, T, C, G, float(eps))
 
 
 def groupnorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, B, T, C, G):
-    _need_cuda(dy, x, dx)
-    _lib.check(_lib.load().bmhrl_groupnorm_bwd(dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                               dx.data_ptr(), _p(dgamma), _p(dbeta), B, T, C, G, stream()), "bmhrl_groupnorm_bwd")
+    _launch("bmhrl_groupnorm_bwd", dy, x, gamma, mean, rstd, dx, dgamma, dbeta, B, T, C, G)
 
 
 # ---- beam-search decoding (csrc/beam.hip)
@@ -819,15 +722,12 @@ def beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_live, B, 
     """per sample, the K best candidates of rule 3 (see bmhrl_beam_select in include/bmhrl_hip.h): scores (B*K) fp32 and
     finished (B*K) uint8 are updated in place unless *_out are given; parent (B*K) int32, tok (B*K) int64,
     hist (B*K, cols) int64 column t + 1, last_live (1,) int32 = t + 1 when a beam is still live.  t: (1,) int64 device word."""
-    _need_cuda(logp, scores, finished, parent, tok, hist, t, last_live)
     scores_out = scores if scores_out is None else scores_out
     finished_out = finished if finished_out is None else finished_out
     _check_select_buffers("beam_select", "K <= V", K, 1, V, ld, logp, scores, scores_out, finished, finished_out, parent, tok,
                           hist, t, last_live, B * K)
-    _lib.check(_lib.load().bmhrl_beam_select(logp.data_ptr(), ld, scores.data_ptr(), finished.data_ptr(), scores_out.data_ptr(),
-                                             finished_out.data_ptr(), parent.data_ptr(), tok.data_ptr(), hist.data_ptr(),
-                                             hist.stride(0), hist.shape[1], t.data_ptr(), last_live.data_ptr(), B, K, V, end_idx,
-                                             pad_idx, stream()), "bmhrl_beam_select")
+    _launch("bmhrl_beam_select", logp, ld, scores, finished, scores_out, finished_out, parent, tok, hist, hist.stride(0),
+            hist.shape[1], t, last_live, B, K, V, end_idx, pad_idx)
 
 
 def group_beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_live, B, K, V, end_idx, pad_idx, G,
@@ -836,7 +736,6 @@ def group_beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_liv
     decode.py, see bmhrl_group_beam_select in include/bmhrl_hip.h): the K beams of a sample form G groups of K / G that choose
     one after another, a later group paying diversity_penalty per earlier beam that chose the token.  Buffers and outputs as
     beam_select's."""
-    _need_cuda(logp, scores, finished, parent, tok, hist, t, last_live)
     scores_out = scores if scores_out is None else scores_out
     finished_out = finished if finished_out is None else finished_out
     lam = float(diversity_penalty)
@@ -844,10 +743,8 @@ def group_beam_select(logp, ld, scores, finished, parent, tok, hist, t, last_liv
                           finished_out, parent, tok, hist, t, last_live, B * K)
     if not (lam >= 0 and lam < float("inf")):
         raise ValueError(f"group_beam_select: diversity_penalty must be finite and >= 0, got {diversity_penalty}")
-    _lib.check(_lib.load().bmhrl_group_beam_select(
-        logp.data_ptr(), ld, scores.data_ptr(), finished.data_ptr(), scores_out.data_ptr(), finished_out.data_ptr(),
-        parent.data_ptr(), tok.data_ptr(), hist.data_ptr(), hist.stride(0), hist.shape[1], t.data_ptr(), last_live.data_ptr(),
-        B, K, V, end_idx, pad_idx, G, lam, stream()), "bmhrl_group_beam_select")
+    _launch("bmhrl_group_beam_select", logp, ld, scores, finished, scores_out, finished_out, parent, tok, hist, hist.stride(0),
+            hist.shape[1], t, last_live, B, K, V, end_idx, pad_idx, G, lam)
 
 
 def beam_reorder_table(buffers, rows, device):
@@ -863,7 +760,7 @@ def beam_reorder_table(buffers, rows, device):
         beam_bytes = state.numel() // rows * state.element_size()
         if pos_bytes < 0 or pos_bytes > beam_bytes:
             raise ValueError("beam_reorder_table: pos_bytes out of range")
-        words += [state.data_ptr(), scratch.data_ptr(), beam_bytes, pos_bytes]
+        words += [_ptr(state), _ptr(scratch), beam_bytes, pos_bytes]
         n_blocks += rows * (-(-beam_bytes // BEAM_REORDER_CHUNK))
     table = torch.tensor(words, dtype=torch.int64).to(device)
     return table, n_blocks
@@ -872,11 +769,9 @@ def beam_reorder_table(buffers, rows, device):
 def beam_reorder(table, n_buffers, n_blocks, parent, rows, K, t, phase):
     """phase 0: scratch[j] = rows [0, t] of state[parent row of j]; phase 1: state[j] = scratch[j] (rows j whose parent is
     themselves are skipped in both); see bmhrl_beam_reorder in include/bmhrl_hip.h"""
-    _need_cuda(table, parent, t)
     if table.dtype != torch.int64 or table.numel() != 4 * n_buffers or parent.dtype != torch.int32 or parent.numel() < rows:
         raise ValueError("beam_reorder: table of n_buffers x 4 int64 words and an int32 parent per row expected")
-    _lib.check(_lib.load().bmhrl_beam_reorder(table.data_ptr(), n_buffers, n_blocks, parent.data_ptr(), rows, K, t.data_ptr(),
-                                              phase, stream()), "bmhrl_beam_reorder")
+    _launch("bmhrl_beam_reorder", table, n_buffers, n_blocks, parent, rows, K, t, phase)
 
 
 # ---- per-prefix caption rewards (csrc/rewards.hip)
@@ -888,7 +783,6 @@ def rewards(hyp, vmap, eos, ref, ref_len, df_keys, df_logs, metric, n, sigma, sc
     """per-prefix scores (B, L) fp64 and their first differences (B, L) fp32 of the sampled captions hyp (B, L) int64 against
     ref (>= B, R) int32 word ids, ref_len (>= B) int32; see bmhrl_rewards in include/bmhrl_hip.h.  df_keys (cap, 4) int32 /
     df_logs (cap) fp64: the CIDEr document-frequency table (None for BLEU)."""
-    _need_cuda(hyp, vmap, ref, ref_len, df_keys, df_logs, scores, delta)
     B, L = hyp.shape
     R = ref.shape[1]
     if hyp.dtype != torch.int64 or vmap.dtype != torch.int32 or ref.dtype != torch.int32 or ref_len.dtype != torch.int32:
@@ -906,10 +800,8 @@ def rewards(hyp, vmap, eos, ref, ref_len, df_keys, df_logs, metric, n, sigma, sc
         if df_keys.dtype != torch.int32 or tuple(df_keys.shape) != (cap, 4) or not df_keys.is_contiguous() or \
                 df_logs.dtype != torch.float64 or df_logs.numel() != cap:
             raise ValueError("rewards: df_keys (cap, 4) int32 and df_logs (cap) fp64 expected")
-    _lib.check(_lib.load().bmhrl_rewards(hyp.data_ptr(), hyp.stride(0), vmap.data_ptr(), vmap.numel(), eos, ref.data_ptr(),
-                                         ref.stride(0), ref_len.data_ptr(), _p(df_keys), _p(df_logs), cap, metric, n,
-                                         float(sigma), B, L, R, scores.data_ptr(), scores.stride(0), delta.data_ptr(),
-                                         delta.stride(0), stream()), "bmhrl_rewards")
+    _launch("bmhrl_rewards", hyp, hyp.stride(0), vmap, vmap.numel(), eos, ref, ref.stride(0), ref_len, df_keys, df_logs, cap,
+            metric, n, float(sigma), B, L, R, scores, scores.stride(0), delta, delta.stride(0))
 
 
 # ---- per-prefix METEOR rewards (csrc/meteor.hip)
@@ -918,7 +810,6 @@ def meteor(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, alpha, be
     captions hyp (B, L) int64 against ref (>= B, R) int32 word ids, ref_len (>= B) int32; see bmhrl_meteor in
     include/bmhrl_hip.h.  vstem (V) int32 with ref_stem shaped and strided like ref (both None: no stem stage); syn_off
     (V + 1) int32 and syn_ids int32, at least one element (both None: no synonym stage)."""
-    _need_cuda(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, scores, delta)
     B, L = hyp.shape
     R = ref.shape[1]
     V = vmap.numel()
@@ -944,10 +835,8 @@ def meteor(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, alpha, be
     if scores.dtype != torch.float64 or delta.dtype != torch.float32 or tuple(scores.shape) != (B, L) or \
             tuple(delta.shape) != (B, L) or scores.stride(1) != 1 or delta.stride(1) != 1:
         raise ValueError("meteor: scores (B, L) fp64 and delta (B, L) fp32 with contiguous rows expected")
-    _lib.check(_lib.load().bmhrl_meteor(hyp.data_ptr(), hyp.stride(0), vmap.data_ptr(), _p(vstem), V, _p(syn_off), _p(syn_ids),
-                                        n_syn, ref.data_ptr(), _p(ref_stem), ref.stride(0), ref_len.data_ptr(), float(alpha),
-                                        float(beta), float(gamma), B, L, R, scores.data_ptr(), scores.stride(0),
-                                        delta.data_ptr(), delta.stride(0), stream()), "bmhrl_meteor")
+    _launch("bmhrl_meteor", hyp, hyp.stride(0), vmap, vstem, V, syn_off, syn_ids, n_syn, ref, ref_stem, ref.stride(0), ref_len,
+            float(alpha), float(beta), float(gamma), B, L, R, scores, scores.stride(0), delta, delta.stride(0))
 
 
 # ---- evaluation forms of the caption metrics (csrc/caption_eval.hip)
@@ -960,7 +849,6 @@ def caption_eval(hyp, hyp_len, ref, ref_len, group_off):
     hyp (P, L) / ref (P, R) int32 word ids with contiguous rows, hyp_len / ref_len (P) int32.  Returns pair_ints (P, 10)
     int32, pair_lcs (P) int32, pair_cider (P) fp64, group_scores (G, 6) fp64.  Synchronises the stream once (the offsets
     are checked on the host); not for captured graphs."""
-    _need_cuda(hyp, hyp_len, ref, ref_len, group_off)
     for t in (hyp, hyp_len, ref, ref_len, group_off):
         if t.dtype != torch.int32:
             raise ValueError("caption_eval: int32 tensors expected")
@@ -977,10 +865,8 @@ def caption_eval(hyp, hyp_len, ref, ref_len, group_off):
     pair_lcs = torch.empty(max(P, 0), dtype=torch.int32, device=dev)
     pair_cider = torch.empty(max(P, 0), dtype=torch.float64, device=dev)
     group_scores = torch.empty(max(G, 0), CAPTION_EVAL_GROUP_SCORES, dtype=torch.float64, device=dev)
-    _lib.check(_lib.load().bmhrl_caption_eval(hyp.data_ptr(), hyp.stride(0), hyp_len.data_ptr(), ref.data_ptr(), ref.stride(0),
-                                              ref_len.data_ptr(), group_off.data_ptr(), P, G, L, R, pair_ints.data_ptr(),
-                                              pair_lcs.data_ptr(), pair_cider.data_ptr(), group_scores.data_ptr(), stream()),
-               "bmhrl_caption_eval")
+    _launch("bmhrl_caption_eval", hyp, hyp.stride(0), hyp_len, ref, ref.stride(0), ref_len, group_off, P, G, L, R, pair_ints,
+            pair_lcs, pair_cider, group_scores)
     return pair_ints, pair_lcs, pair_cider, group_scores
 
 
@@ -1006,7 +892,6 @@ def meteor_matrix(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, hy
     members, hyp_off / ref_off (G + 1) int32 and cell_off (G + 1) int64 delimit the groups.  vmap, vstem, syn_off, syn_ids
     as ops.meteor takes them.  Synchronises the stream once (offsets and indices are checked on the host); not for
     captured graphs."""
-    _need_cuda(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, hyp_idx, ref_idx, hyp_off, ref_off, cell_off, S)
     G = _soda_offsets("meteor_matrix", hyp_off, ref_off, cell_off)
     V = vmap.numel()
     if hyp.dtype != torch.int64 or vmap.dtype != torch.int32 or ref.dtype != torch.int32 or ref_len.dtype != torch.int32 or \
@@ -1031,12 +916,9 @@ def meteor_matrix(hyp, vmap, vstem, syn_off, syn_ids, ref, ref_stem, ref_len, hy
             raise ValueError("meteor_matrix: syn_off (V + 1) int32 and syn_ids (>= 1) int32 expected")
     if S.dtype != torch.float64 or S.dim() != 1 or not S.is_contiguous():
         raise ValueError("meteor_matrix: S (cells) fp64, contiguous, expected")
-    _lib.check(_lib.load().bmhrl_meteor_matrix(
-        hyp.data_ptr(), hyp.stride(0), hyp.shape[0], hyp.shape[1], vmap.data_ptr(), _p(vstem), V, _p(syn_off), _p(syn_ids),
-        n_syn, ref.data_ptr(), _p(ref_stem), ref.stride(0), ref_len.data_ptr(), ref.shape[0], ref.shape[1],
-        hyp_idx.data_ptr(), hyp_idx.numel(), ref_idx.data_ptr(), ref_idx.numel(), hyp_off.data_ptr(), ref_off.data_ptr(),
-        cell_off.data_ptr(), G, float(alpha), float(beta), float(gamma), S.data_ptr(), S.numel(), stream()),
-        "bmhrl_meteor_matrix")
+    _launch("bmhrl_meteor_matrix", hyp, hyp.stride(0), hyp.shape[0], hyp.shape[1], vmap, vstem, V, syn_off, syn_ids, n_syn, ref,
+            ref_stem, ref.stride(0), ref_len, ref.shape[0], ref.shape[1], hyp_idx, hyp_idx.numel(), ref_idx, ref_idx.numel(),
+            hyp_off, ref_off, cell_off, G, float(alpha), float(beta), float(gamma), S, S.numel())
 
 
 def soda_dp(pred_seg, ref_seg, hyp_off, ref_off, cell_off, S, tious):
@@ -1044,7 +926,6 @@ def soda_dp(pred_seg, ref_seg, hyp_off, ref_off, cell_off, S, tious):
     tIoU x S per group and threshold; see bmhrl_soda_dp in include/bmhrl_hip.h.  pred_seg (sum P, 2) / ref_seg (sum R, 2)
     fp64 start, end in matching order; the offsets and S as ops.meteor_matrix; tious (T) fp64 on the device.  Synchronises
     the stream once; not for captured graphs."""
-    _need_cuda(pred_seg, ref_seg, hyp_off, ref_off, cell_off, S, tious)
     G = _soda_offsets("soda_dp", hyp_off, ref_off, cell_off)
     for t in (pred_seg, ref_seg):
         if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 2 or not t.is_contiguous():
@@ -1054,9 +935,8 @@ def soda_dp(pred_seg, ref_seg, hyp_off, ref_off, cell_off, S, tious):
         raise ValueError("soda_dp: S (cells) and tious (T) fp64, contiguous, expected")
     T = tious.numel()
     out = torch.empty(max(G, 0), T, 4, dtype=torch.float64, device=S.device)
-    _lib.check(_lib.load().bmhrl_soda_dp(pred_seg.data_ptr(), pred_seg.shape[0], ref_seg.data_ptr(), ref_seg.shape[0],
-                                         hyp_off.data_ptr(), ref_off.data_ptr(), cell_off.data_ptr(), G, S.data_ptr(), S.numel(),
-                                         tious.data_ptr(), T, out.data_ptr(), stream()), "bmhrl_soda_dp")
+    _launch("bmhrl_soda_dp", pred_seg, pred_seg.shape[0], ref_seg, ref_seg.shape[0], hyp_off, ref_off, cell_off, G, S, S.numel(),
+            tious, T, out)
     return out
 
 
@@ -1119,11 +999,8 @@ def tiou_hits(pred_seg, ref_seg, groups, tious, strict, out=None):
                torch.empty(T, groups.sum_r, dtype=torch.int32, device=pred_seg.device))
     pred_hits, ref_first = out
     ldp, ldr = _tiou_out("tiou_hits", pred_hits, T, groups.sum_p), _tiou_out("tiou_hits", ref_first, T, groups.sum_r)
-    _need_cuda(pred_seg, ref_seg, groups.groups, groups.out_off, tious, pred_hits, ref_first)
-    _lib.check(_lib.load().bmhrl_tiou_hits(pred_seg.data_ptr(), pred_seg.shape[0], ref_seg.data_ptr(), ref_seg.shape[0],
-                                           groups.host.ctypes.data, groups.groups.data_ptr(), groups.out_off.data_ptr(),
-                                           groups.G, tious.data_ptr(), T, int(bool(strict)), pred_hits.data_ptr(), ldp,
-                                           ref_first.data_ptr(), ldr, stream()), "bmhrl_tiou_hits")
+    _launch("bmhrl_tiou_hits", pred_seg, pred_seg.shape[0], ref_seg, ref_seg.shape[0], groups.host.ctypes.data, groups.groups,
+            groups.out_off, groups.G, tious, T, int(bool(strict)), pred_hits, ldp, ref_first, ldr)
     return pred_hits[:, :groups.sum_p], ref_first[:, :groups.sum_r]
 
 
@@ -1142,11 +1019,8 @@ def tiou_pairs(pred_seg, ref_seg, groups, tiou, pair_off, n_pairs, out=None):
         out = torch.empty(n_pairs, dtype=torch.int32, device=pred_seg.device)
     if out.dtype != torch.int32 or out.dim() != 1 or out.numel() < n_pairs or not out.is_contiguous():
         raise ValueError("tiou_pairs: out must be a contiguous int32 tensor of at least n_pairs words")
-    _need_cuda(pred_seg, ref_seg, groups.groups, groups.out_off, pair_off, out)
-    _lib.check(_lib.load().bmhrl_tiou_pairs(pred_seg.data_ptr(), pred_seg.shape[0], ref_seg.data_ptr(), ref_seg.shape[0],
-                                            groups.host.ctypes.data, groups.groups.data_ptr(), groups.out_off.data_ptr(),
-                                            groups.G, float(tiou), pair_off.data_ptr(), groups.sum_p, out.data_ptr(), n_pairs,
-                                            stream()), "bmhrl_tiou_pairs")
+    _launch("bmhrl_tiou_pairs", pred_seg, pred_seg.shape[0], ref_seg, ref_seg.shape[0], groups.host.ctypes.data, groups.groups,
+            groups.out_off, groups.G, float(tiou), pair_off, groups.sum_p, out, n_pairs)
     return out[:n_pairs]
 
 
@@ -1160,7 +1034,6 @@ def sample_step(logp, ld, rows, V, temperature, top_k, top_p, seed, seed_dev, t,
     fp32; finished (rows) uint8 / bool, tok (rows) int64, sum_logp (rows) fp32 updated in place; out (rows, cols) int64 gets
     column t + 1, step_logp / step_logq (rows, cols) fp32 (optional, the same row stride) column t.  seed_dev: None or a
     (1,) int64 word added to seed (uint64 wraparound); t: (1,) int64 device word."""
-    _need_cuda(logp, seed_dev, t, finished, tok, out, sum_logp, step_logp, step_logq)
     if not (1 <= V <= SAMPLE_MAX_V and ld >= V and rows >= 1 and logp.dtype == torch.float32
             and logp.numel() >= (rows - 1) * ld + V):
         raise ValueError(f"sample_step: need 1 <= V <= {SAMPLE_MAX_V} and fp32 logp rows (rows, ld >= V)")
@@ -1178,11 +1051,8 @@ def sample_step(logp, ld, rows, V, temperature, top_k, top_p, seed, seed_dev, t,
             raise ValueError("sample_step: step_logp / step_logq must be fp32 with the shape and strides of out")
     if t.dtype != torch.int64 or (seed_dev is not None and seed_dev.dtype != torch.int64):
         raise ValueError("sample_step: t and seed_dev are int64 words")
-    _lib.check(_lib.load().bmhrl_sample_step(logp.data_ptr(), ld, rows, V, float(temperature), int(top_k), float(top_p),
-                                             int(seed), _p(seed_dev), t.data_ptr(), row_offset, end_idx, pad_idx,
-                                             finished.data_ptr(), tok.data_ptr(), out.data_ptr(), out.stride(0),
-                                             sum_logp.data_ptr(), _p(step_logp), _p(step_logq), stream()),
-               "bmhrl_sample_step")
+    _launch("bmhrl_sample_step", logp, ld, rows, V, float(temperature), int(top_k), float(top_p), int(seed), seed_dev, t,
+            row_offset, end_idx, pad_idx, finished, tok, out, out.stride(0), sum_logp, step_logp, step_logq)
 
 
 # ---- constrained caption decoding (csrc/constrain.hip)
@@ -1193,7 +1063,6 @@ def logit_rules(logp, ld, rows, V, hist, t, ngram, min_len, penalty, end_idx, pa
     """repetition penalty, no-repeat n-gram ban and minimum length on every row of logp (rows, ld >= V) fp32, in place (see
     bmhrl_logit_rules in include/bmhrl_hip.h): hist (rows, cols <= LOGIT_RULES_MAX_HIST) int64 holds the rows' sequences,
     columns 0 .. t; t: (1,) int64 device word."""
-    _need_cuda(logp, hist, t)
     if not (V >= 1 and ld >= V and rows >= 1 and logp.dtype == torch.float32 and logp.numel() >= (rows - 1) * ld + V):
         raise ValueError("logit_rules: need V >= 1 and fp32 logp rows (rows, ld >= V)")
     if not (ngram >= 0 and min_len >= 0 and math.isfinite(penalty) and penalty > 0):
@@ -1205,9 +1074,8 @@ def logit_rules(logp, ld, rows, V, hist, t, ngram, min_len, penalty, end_idx, pa
         raise ValueError(f"logit_rules: hist must be a contiguous (rows, cols <= {LOGIT_RULES_MAX_HIST}) int64 buffer")
     if t.dtype != torch.int64:
         raise ValueError("logit_rules: t is an int64 word")
-    _lib.check(_lib.load().bmhrl_logit_rules(logp.data_ptr(), ld, rows, V, hist.data_ptr(), hist.stride(0), t.data_ptr(),
-                                             int(ngram), int(min_len), float(penalty), end_idx, pad_idx, stream()),
-               "bmhrl_logit_rules")
+    _launch("bmhrl_logit_rules", logp, ld, rows, V, hist, hist.stride(0), t, int(ngram), int(min_len), float(penalty), end_idx,
+            pad_idx)
 
 
 # ---- consensus choice among a clip's hypotheses (csrc/consensus.hip)
@@ -1220,7 +1088,8 @@ def consensus(hist, steps, K, end_idx, n=4, token_weight=None, pair=False):
     token history: K consecutive rows per clip, column 0 the start token, columns 1 .. steps the generated tokens (see
     bmhrl_consensus in include/bmhrl_hip.h).  n: the largest gram length; token_weight: None or (V,) fp32 on hist's device;
     pair=True: also the pairwise utilities (B, K, K) fp64, u(i, i) written as 0."""
-    _need_cuda(hist, token_weight)
+    for t in (hist, token_weight):
+        _ptr(t)                         # (CPU memory is refused before the devices are compared below)
     steps, K, n = int(steps), int(K), int(n)
     if not (1 <= K <= BEAM_MAX and 0 <= steps <= CONSENSUS_MAX_STEPS and 1 <= n <= CONSENSUS_MAX_N):
         raise ValueError(f"consensus: need 1 <= K <= {BEAM_MAX}, 0 <= steps <= {CONSENSUS_MAX_STEPS} and "
@@ -1237,8 +1106,7 @@ def consensus(hist, steps, K, end_idx, n=4, token_weight=None, pair=False):
     B = hist.shape[0] // K
     util = torch.empty(B, K, dtype=torch.float64, device=hist.device)
     pairs = torch.empty(B, K, K, dtype=torch.float64, device=hist.device) if pair else None
-    _lib.check(_lib.load().bmhrl_consensus(hist.data_ptr(), hist.stride(0), B, K, steps, int(end_idx), n, _p(token_weight), V,
-                                           util.data_ptr(), _p(pairs), stream()), "bmhrl_consensus")
+    _launch("bmhrl_consensus", hist, hist.stride(0), B, K, steps, int(end_idx), n, token_weight, V, util, pairs)
     return (util, pairs) if pair else util
 
 
@@ -1264,7 +1132,6 @@ def word_cost(logits, captions, pad_idx, cost_scale=1.0):
     may sit in a wider buffer (any row stride >= C), captions (B, L) int64.  Returns words (B, L) int32, n_words (B) int32,
     lse (2, B, Q) -- the log-sum-exp and the rounding residue of its last addition, an fp32 pair the later launches subtract
     together --, x_none (B, Q), gathered (B, Q, L) and cost (B, Q, L) fp32."""
-    _need_cuda(logits, captions)
     if logits.dim() != 3 or captions.dim() != 2 or captions.dtype != torch.int64 or captions.shape[0] != logits.shape[0] or \
             (captions.shape[1] > 1 and captions.stride(1) != 1):
         raise ValueError("word_cost: logits (B, Q, C) fp32 and captions (B, L) int64 with contiguous rows expected")
@@ -1278,17 +1145,14 @@ def word_cost(logits, captions, pad_idx, cost_scale=1.0):
     x_none = torch.empty(B, Q, device=dev)
     gathered = torch.empty(B, Q, L, device=dev)
     cost = torch.empty(B, Q, L, device=dev)
-    _lib.check(_lib.load().bmhrl_word_cost(logits.data_ptr(), ld, captions.data_ptr(), captions.stride(0) if B > 1 else max(L, 1),
-                                           int(pad_idx), float(cost_scale), B, Q, L, Cn, words.data_ptr(), n_words.data_ptr(),
-                                           lse[0].data_ptr(), lse[1].data_ptr(), x_none.data_ptr(), gathered.data_ptr(),
-                                           cost.data_ptr(), stream()), "bmhrl_word_cost")
+    _launch("bmhrl_word_cost", logits, ld, captions, captions.stride(0) if B > 1 else max(L, 1), int(pad_idx), float(cost_scale),
+            B, Q, L, Cn, words, n_words, lse[0], lse[1], x_none, gathered, cost)
     return words, n_words, lse, x_none, gathered, cost
 
 
 def lsa_match(cost, n, out=None):
     """minimum-cost assignment per sample (see bmhrl_lsa_match): cost (B, Q, L) fp32 with any positive strides, n (B) int32
     targets per sample.  Returns query_of_target (B, L) int32: a distinct query for each target j < n[b], -1 behind them."""
-    _need_cuda(cost, n, out)
     if cost.dim() != 3 or cost.dtype != torch.float32 or n.dtype != torch.int32 or n.numel() != cost.shape[0] or \
             not n.is_contiguous():
         raise ValueError("lsa_match: cost (B, Q, L) fp32 and n (B) int32 expected")
@@ -1298,15 +1162,13 @@ def lsa_match(cost, n, out=None):
     elif out.dtype != torch.int32 or tuple(out.shape) != (B, L) or not out.is_contiguous():
         raise ValueError("lsa_match: out must be a contiguous (B, L) int32 tensor")
     sb, sq, sl = (s if d > 1 else 1 for s, d in zip(cost.stride(), cost.shape))
-    _lib.check(_lib.load().bmhrl_lsa_match(cost.data_ptr(), sb, sq, sl, n.data_ptr(), B, Q, L, out.data_ptr(), stream()),
-               "bmhrl_lsa_match")
+    _launch("bmhrl_lsa_match", cost, sb, sq, sl, n, B, Q, L, out)
     return out
 
 
 def word_loss(words, n_words, query_of_target, lse, x_none, gathered, eos_coef, C):
     """class map, row weights and the weighted mean (see bmhrl_word_loss).  Returns tgt_class (B, Q) int32, row_w (B, Q)
     fp32 and loss_scale (2,) fp32 = [loss, 1 / sum row_w]."""
-    _need_cuda(words, n_words, query_of_target, lse, x_none, gathered)
     if gathered.dim() != 3:
         raise ValueError("word_loss: gathered must be (B, Q, L)")
     B, Q, L = gathered.shape
@@ -1318,10 +1180,8 @@ def word_loss(words, n_words, query_of_target, lse, x_none, gathered, eos_coef, 
     tgt_class = torch.empty(B, Q, dtype=torch.int32, device=dev)
     row_w = torch.empty(B, Q, device=dev)
     loss_scale = torch.empty(2, device=dev)
-    _lib.check(_lib.load().bmhrl_word_loss(words.data_ptr(), n_words.data_ptr(), query_of_target.data_ptr(), lse[0].data_ptr(),
-                                           lse[1].data_ptr(), x_none.data_ptr(), gathered.data_ptr(), float(eos_coef), B, Q, L, int(C),
-                                           tgt_class.data_ptr(), row_w.data_ptr(), loss_scale.data_ptr(), stream()),
-               "bmhrl_word_loss")
+    _launch("bmhrl_word_loss", words, n_words, query_of_target, lse[0], lse[1], x_none, gathered, float(eos_coef), B, Q, L, int(C),
+            tgt_class, row_w, loss_scale)
     return tgt_class, row_w, loss_scale
 
 
@@ -1330,7 +1190,6 @@ def word_loss_bwd(logits, lse, tgt_class, row_w, loss_scale, g=None, out=None):
     returns them; g: None or a (1,) fp32
     device scalar, the incoming gradient; out: None or (B, Q, C) fp32 rows in a buffer of any row stride >= C, whose
     padding columns are left alone."""
-    _need_cuda(logits, lse, tgt_class, row_w, loss_scale, g, out)
     if logits.dim() != 3:
         raise ValueError("word_loss_bwd: logits must be (B, Q, C)")
     B, Q, Cn = logits.shape
@@ -1344,9 +1203,7 @@ def word_loss_bwd(logits, lse, tgt_class, row_w, loss_scale, g=None, out=None):
             raise ValueError(f"word_loss_bwd: expected a contiguous {dt} tensor of {n} elements")
     if g is not None and (g.dtype != torch.float32 or g.numel() != 1):
         raise ValueError("word_loss_bwd: g is a (1,) fp32 device scalar")
-    _lib.check(_lib.load().bmhrl_word_loss_bwd(logits.data_ptr(), ld, lse.data_ptr(), lse.data_ptr() + 4 * B * Q,
-                                               tgt_class.data_ptr(), row_w.data_ptr(), loss_scale.data_ptr(), _p(g), out.data_ptr(), ldd, B, Q, Cn, stream()),
-               "bmhrl_word_loss_bwd")
+    _launch("bmhrl_word_loss_bwd", logits, ld, lse, _at(lse, B * Q), tgt_class, row_w, loss_scale, g, out, ldd, B, Q, Cn)
     return out
 
 
@@ -1365,7 +1222,6 @@ def proposal_assign(targets, anchors, cell_sec, B, S):
     """target assignment of one modality (see bmhrl_proposal_assign): targets (N, 4) fp32 rows [video index, centre s,
     length s, meta index], anchors (A) fp32 seconds.  Returns owner (B, A, S) int32 (the target row that owns the cell, -1
     for none), tx (N), tw (N) fp32 and counts (2) int32 = [owned cells, the others], all on the device."""
-    _need_cuda(targets, anchors)
     if targets.dim() != 2 or targets.shape[1] != 4 or anchors.dim() != 1:
         raise ValueError("proposal_assign: targets (N, 4) and anchors (A) expected")
     N, A = targets.shape[0], anchors.shape[0]
@@ -1376,10 +1232,8 @@ def proposal_assign(targets, anchors, cell_sec, B, S):
     tx = torch.empty(N, device=dev)
     tw = torch.empty(N, device=dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().bmhrl_proposal_assign(targets.data_ptr() if N else None, N, anchors.data_ptr(), A, float(cell_sec),
-                                                 int(B), int(S), owner.data_ptr(), tx.data_ptr() if N else None,
-                                                 tw.data_ptr() if N else None, counts.data_ptr(), stream()),
-               "bmhrl_proposal_assign")
+    _launch("bmhrl_proposal_assign", targets if N else None, N, anchors, A, float(cell_sec), int(B), int(S), owner,
+            tx if N else None, tw if N else None, counts)
     return owner, tx, tw, counts
 
 
@@ -1389,7 +1243,6 @@ def proposal_head(x, anchors, cell_sec, pred, row_off, assigned=None, obj_coeff=
     rows row_off .. row_off + A*S - 1 are written.  assigned = proposal_assign's (owner, tx, tw, counts) selects training:
     sums (5) fp32 = [loss_x, loss_w, loss_obj, loss_noobj, total] is written (allocated when None) and dx (B, S, 3A), when
     given, gets dscale * d total / d x.  assigned=None is inference: predictions only.  Returns sums (None in inference)."""
-    _need_cuda(x, anchors, pred, sums, dx, dscale)
     if x.dim() != 3 or anchors.dim() != 1 or x.shape[2] != 3 * anchors.shape[0] or pred.dim() != 3:
         raise ValueError("proposal_head: x (B, S, 3A), anchors (A) and pred (B, N_total, 3) expected")
     B, S, A = x.shape[0], x.shape[1], anchors.shape[0]
@@ -1414,10 +1267,8 @@ def proposal_head(x, anchors, cell_sec, pred, row_off, assigned=None, obj_coeff=
         counter = torch.empty(4, dtype=torch.int32, device=dev)        # the ticket word (the call zeroes it on the stream)
     elif dx is not None or sums is not None:
         raise ValueError("proposal_head: sums and dx need assigned targets")
-    _lib.check(_lib.load().bmhrl_proposal_head(x.data_ptr(), anchors.data_ptr(), float(cell_sec), B, S, A, pred.data_ptr(),
-                                               pred.shape[1], int(row_off), _p(owner), _p(tx), _p(tw), _p(counts),
-                                               float(obj_coeff), float(noobj_coeff), _p(dscale), _p(dx), _p(sums), _p(partials),
-                                               _p(counter), stream()), "bmhrl_proposal_head")
+    _launch("bmhrl_proposal_head", x, anchors, float(cell_sec), B, S, A, pred, pred.shape[1], int(row_off), owner, tx, tw, counts,
+            float(obj_coeff), float(noobj_coeff), dscale, dx, sums, partials, counter)
     return sums
 
 
@@ -1433,7 +1284,6 @@ def proposal_select(predictions, durations, k, nms_tiou=None):
     """top-k + corner coordinates + trimming + greedy NMS of a batch (see bmhrl_proposal_select): predictions (B, N, 3) fp32
     rows [centre s, length s, confidence], durations (B) fp32, nms_tiou None = no suppression.  Returns props (B, k, 3) =
     [start, end, confidence], survivors first in confidence order and zeros behind them, and count (B) int32."""
-    _need_cuda(predictions, durations)
     if predictions.dim() != 3 or predictions.shape[2] != 3:
         raise ValueError("proposal_select: predictions (B, N, 3) expected")
     B, N = predictions.shape[0], predictions.shape[1]
@@ -1445,9 +1295,8 @@ def proposal_select(predictions, durations, k, nms_tiou=None):
     count = torch.empty(B, dtype=torch.int32, device=dev)
     words = B * proposal_select_workspace(N, k) if 1 <= k <= PROPOSAL_MAX_K else 0
     ws = torch.empty(words, dtype=torch.int64, device=dev) if words else None
-    _lib.check(_lib.load().bmhrl_proposal_select(predictions.data_ptr(), B, N, durations.data_ptr(), k,
-                                                 -1.0 if nms_tiou is None else float(nms_tiou), props.data_ptr(),
-                                                 count.data_ptr(), _p(ws), words, stream()), "bmhrl_proposal_select")
+    _launch("bmhrl_proposal_select", predictions, B, N, durations, k, -1.0 if nms_tiou is None else float(nms_tiou), props, count,
+            ws, words)
     return props, count
 
 
@@ -1458,7 +1307,8 @@ def crop_segments(src, src_len, durations, seg_video, seg_times, pad_value, T_ou
     end].  Returns out (P, T_out, D) fp32, lengths (P) int32 (the crop's row count, not clipped to T_out), lo (P) int32 (its
     first row) and status (2) int32 = [segments longer than T_out, segments without a defined crop], all on the device;
     nothing is read back.  `out`: a contiguous (P, T_out, D) fp32 tensor to fill instead of a new one."""
-    _need_cuda(src, src_len, durations, seg_video, seg_times, out)
+    for t in (src, src_len, durations, seg_video, seg_times, out):
+        _ptr(t)                         # (CPU memory is refused before the devices are compared below)
     if src.dim() != 3 or seg_times.dim() != 2:
         raise ValueError("crop_segments: src (V, S_pad, D) and seg_times (P, 2) expected")
     V, S_pad, D = src.shape
@@ -1482,10 +1332,8 @@ def crop_segments(src, src_len, durations, seg_video, seg_times, pad_value, T_ou
     lengths = torch.empty(P, dtype=torch.int32, device=dev)
     lo = torch.empty(P, dtype=torch.int32, device=dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().bmhrl_crop_segments(src.data_ptr(), src_len.data_ptr(), durations.data_ptr(), V, S_pad, D,
-                                               seg_video.data_ptr(), seg_times.data_ptr(), P, float(pad_value), T_out,
-                                               out.data_ptr(), lengths.data_ptr(), lo.data_ptr(), status.data_ptr(), stream()),
-               "bmhrl_crop_segments")
+    _launch("bmhrl_crop_segments", src, src_len, durations, V, S_pad, D, seg_video, seg_times, P, float(pad_value), T_out, out,
+            lengths, lo, status)
     return out, lengths, lo, status
 
 
@@ -1507,7 +1355,6 @@ def rollout_advantage(toks, n, m, end_idx, scores, baseline=BASELINE_LEAVE_ONE_O
     -> (len (B * n,) int32, reward (B * n,) fp64, adv (B * n,) fp64, weight (B * n, m) fp32, stats (4,) fp64 = mean reward,
     mean baseline, mean length, token count).  out: the same five tensors to write into (weight may be a view with a wider
     row stride).  Nothing is read on the host."""
-    _need_cuda(toks, scores, base)
     n, m, baseline = int(n), int(m), int(baseline)
     if not (1 <= n <= ROLLOUT_MAX_N and 1 <= m <= REWARDS_MAX_L):
         raise ValueError(f"rollout_advantage: need 1 <= n <= {ROLLOUT_MAX_N} and 1 <= m <= {REWARDS_MAX_L}")
@@ -1529,24 +1376,17 @@ def rollout_advantage(toks, n, m, end_idx, scores, baseline=BASELINE_LEAVE_ONE_O
     for t, dt, k in ((ln, torch.int32, rows), (reward, torch.float64, rows), (adv, torch.float64, rows), (stats, torch.float64, 4)):
         if t.dtype != dt or t.numel() != k or not t.is_contiguous() or t.device != dev:
             raise ValueError("rollout_advantage: len / reward / adv / stats must be contiguous int32 / fp64 tensors on toks' device")
-    _lib.check(_lib.load().bmhrl_rollout_advantage(toks.data_ptr(), ldt, B, n, m, int(end_idx), scores.data_ptr(), lds, baseline,
-                                                   _p(base), ln.data_ptr(), reward.data_ptr(), adv.data_ptr(), weight.data_ptr(),
-                                                   ldw, stats.data_ptr(), stream()), "bmhrl_rollout_advantage")
+    _launch("bmhrl_rollout_advantage", toks, ldt, B, n, m, int(end_idx), scores, lds, baseline, base, ln, reward, adv, weight, ldw,
+            stats)
     return ln, reward, adv, weight[:, :m], stats
 
 
 def policy_loss_fwd(logp, ld, action, weight, logq, clip, ent_weight, row_loss, row_entropy, rows, V):
     """row_loss / row_entropy (rows,) fp32 of bmhrl_policy_loss_fwd: logp (rows, V) fp32 with row stride ld, action (rows,)
     int64, weight (rows,) fp32, logq (rows,) fp32 with clip > 0 (both or neither), ent_weight (rows,) fp32 or None"""
-    _need_cuda(logp, action, weight, logq, ent_weight, row_loss, row_entropy)
-    _lib.check(_lib.load().bmhrl_policy_loss_fwd(logp.data_ptr(), ld, action.data_ptr(), weight.data_ptr(), _p(logq), float(clip),
-                                                 _p(ent_weight), row_loss.data_ptr(), row_entropy.data_ptr(), rows, V, stream()),
-               "bmhrl_policy_loss_fwd")
+    _launch("bmhrl_policy_loss_fwd", logp, ld, action, weight, logq, float(clip), ent_weight, row_loss, row_entropy, rows, V)
 
 
 def policy_loss_bwd(logp, ld, action, weight, logq, clip, ent_weight, gscale, drow, dlogp, ldg, rows, V):
     """the dense gradient dlogp (rows, V) fp32 with row stride ldg of bmhrl_policy_loss_bwd, times gscale[0] * drow[row]"""
-    _need_cuda(logp, action, weight, logq, ent_weight, gscale, drow, dlogp)
-    _lib.check(_lib.load().bmhrl_policy_loss_bwd(logp.data_ptr(), ld, action.data_ptr(), weight.data_ptr(), _p(logq), float(clip),
-                                                 _p(ent_weight), gscale.data_ptr(), drow.data_ptr(), dlogp.data_ptr(), ldg, rows, V,
-                                                 stream()), "bmhrl_policy_loss_bwd")
+    _launch("bmhrl_policy_loss_bwd", logp, ld, action, weight, logq, float(clip), ent_weight, gscale, drow, dlogp, ldg, rows, V)

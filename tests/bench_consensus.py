@@ -50,7 +50,7 @@ def launch_times(B=16, steps=30, N=4, V=40):
         hist = cpu.to(dev)
         util = torch.empty(B, K, dtype=torch.float64, device=dev)
         for tag, wt in (("plain", None), ("weighted", w)):
-            fn = lambda: lib.bmhrl_consensus(hist.data_ptr(), hist.stride(0), B, K, steps, END, N, ops._p(wt),
+            fn = lambda: lib.bmhrl_consensus(hist.data_ptr(), hist.stride(0), B, K, steps, END, N, ops._ptr(wt),
                                              0 if wt is None else V, util.data_ptr(), None, ops.stream())
             res[f"K{K}_{tag}_us"] = [round(timed(fn), 2) for _ in range(2)]
             host = []

@@ -20,9 +20,10 @@ def test_library_builds_and_exports_every_declared_symbol_at_abi_18():
     assert len(syms) >= 24
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/bmhrl_hip.h but not exported"
-    assert set(_lib.PROTOTYPES) | {"bmhrl_hip_arch", "bmhrl_hip_abi_version", "bmhrl_deterministic_enabled", "bmhrl_layernorm_bwd_workspace",
-                                    "bmhrl_attention_shared128_bwd_workspace", "bmhrl_attention_max_keys", "bmhrl_gemm_splits", "bmhrl_small_attention_ok",
-                                    "bmhrl_memory_attention_ok", "bmhrl_gemm_plan", "bmhrl_gemm_group_plan"} == set(syms)
+    assert set(_lib.PROTOTYPES) | set(_lib.QUERIES) == set(syms)
+    assert not set(_lib.PROTOTYPES) & set(_lib.QUERIES)
+    for name, argtypes in _lib.PROTOTYPES.items():         # a launching entry ends in its stream, an address
+        assert argtypes and _lib.PTR_SLOTS[name][-1:] == (len(argtypes) - 1,), name
     assert lib.bmhrl_layernorm_bwd_workspace(4096, 1024) == 256 * 2 * 1024      # 4 rows per wave, 4 waves per block: 256 blocks
     assert lib.bmhrl_hip_arch() == b"gfx950"
     assert lib.bmhrl_hip_abi_version() == 18

@@ -1050,3 +1050,23 @@ def test_attention_fwd_two_phase_form_for_short_memories(dev, B, H, Sq, Sk, kind
     assert torch.equal((Od == 0)[big], (Og == 0)[big])
     kept = big & (Od != 0)
     assert rel_err(Od[kept], (O / 0.75)[kept]) < 1.5e-2
+
+
+def test_at_is_the_address_of_an_element(dev):
+    """ops._at scales an element offset by the tensor's own element size and never moves an address otherwise"""
+    from bmhrl_amd import ops
+    for dt in (torch.bfloat16, torch.float32, torch.int64):
+        t = torch.zeros(8, dtype=dt, device=dev)
+        assert ops._at(t, 3) == t.data_ptr() + 3 * t.element_size()
+        assert ops._at(t, 0) == t.data_ptr() == ops._ptr(t)
+        assert ops._at(t[2:], 3) == t.data_ptr() + 5 * t.element_size()
+    assert ops._at(None, 3) is None and ops._at(None, 0) is None and ops._ptr(None) is None
+
+
+def test_stream_is_the_handle_of_torchs_current_stream(dev):
+    from bmhrl_amd import ops
+    assert ops.stream() == torch.cuda.current_stream().cuda_stream
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        assert ops.stream() == side.cuda_stream == torch.cuda.current_stream().cuda_stream != 0
+    assert ops.stream() == torch.cuda.current_stream().cuda_stream
