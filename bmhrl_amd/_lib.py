@@ -161,6 +161,7 @@ PROTOTYPES = {
     "bmhrl_rollout_advantage": [ptr, i64, i32, i32, i32, i64, ptr, i64, i32, ptr, ptr, ptr, ptr, ptr, i64, ptr, ptr],
     "bmhrl_policy_loss_fwd": [ptr, i64, ptr, ptr, ptr, f32, ptr, ptr, ptr, i64, i32, ptr],
     "bmhrl_policy_loss_bwd": [ptr, i64, ptr, ptr, ptr, f32, ptr, ptr, ptr, ptr, i64, i64, i32, ptr],
+    "bmhrl_ngram_stats": [ptr, i32, ptr, i32, ptr, i32, ptr, ptr],
 }
 
 # QUERIES: name -> (restype, argtypes) of the host-only entries (plans, limits, workspace sizes, build facts): no stream,

@@ -67,7 +67,10 @@ def calculate_metrics(reference_paths, submission_path, tIoUs, max_prop_per_vid,
     evaluation package (and its Java METEOR) on sys.path -- not part of this package.  evaluator "device": this package's
     bmhrl_amd.evaluate.DenseCaptionEvaluator (what its METEOR and tokenizer are: see there), with evaluator_options as its
     keywords (device, tokenizer, stemmer, synonyms; soda=True adds SODA_c, SODA_c_Precision and SODA_c_Recall;
-    proposal_recall=True adds AUC and AR@AN; tiou_backend="device" pairs and detects through the device tIoU tables)."""
+    proposal_recall=True adds AUC and AR@AN; tiou_backend="device" pairs and detects through the device tIoU tables;
+    paragraph=True adds the paragraph-level Para_Bleu_1..4, Para_METEOR, Para_ROUGE_L, Para_CIDEr and the repetition /
+    diversity figures Para_RE_4, Para_XRE_4, Para_Div_1, Para_Div_2, with paragraph_top=k reading only the k best-scored
+    proposals of a video as its paragraph)."""
     fields = ["results", "version", "external_data"]
     if evaluator is None:
         try:
@@ -131,6 +134,9 @@ def validation_1by1_loop(cfg, model, loader, decoder, epoch, TBoard, evaluator=N
         for tag, key in (("meteor", "METEOR"), ("bleu4", "Bleu_4"), ("bleu3", "Bleu_3"), ("precision", "Precision"),
                          ("recall", "Recall")):
             TBoard.add_scalar(f"{phase}/{tag}", avg[key] * 100, epoch)
+        if "Para_METEOR" in avg:      # the evaluator ran with paragraph=True (cfg.caption_evaluator_options)
+            for tag, key in (("para_meteor", "Para_METEOR"), ("para_cider", "Para_CIDEr"), ("para_re4", "Para_RE_4")):
+                TBoard.add_scalar(f"{phase}/{tag}", avg[key] * 100, epoch)
         TBoard.add_scalar(f"{phase}/duration_of_1by1", (time() - t_start) / 60, epoch)
     return val_metrics
 

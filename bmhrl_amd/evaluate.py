@@ -27,6 +27,15 @@ Proposal metrics on the device (tiou_backend="device", proposal_recall=True; seg
 pair_indices_device, proposal_recall): the tIoU tables of every group are evaluated in one launch
 (ops.tiou_hits, csrc/proposal_eval.hip) with the bits of `tiou` below, and detection precision / recall, the caption pairing
 and AR@AN / AUC are built from its integers.
+
+Paragraph evaluation (paragraph=True; paragraph_groups, paragraph_scores, paragraph_stats, paragraph_means; DESIGN.md
+section 33): a video's captions in time order read as one paragraph.  Para_Bleu_1..4 / Para_METEOR / Para_ROUGE_L /
+Para_CIDEr score the predicted paragraph against each ground-truth file's paragraph through score_pairs with one group per
+file; Para_RE_4 / Para_XRE_4 / Para_Div_1 / Para_Div_2 are the n-gram repetition, cross-sentence repetition and diversity
+of the predicted paragraphs, from the exact occurrence counts of one ops.ngram_stats launch (csrc/paragraph.hip).  They are
+written from the definitions in section 33 and have been compared with no published tool; METEOR is the function above,
+and several ground-truth files are averaged where the usual paragraph protocol takes them as multiple references of one
+score.  So the figures are comparable between runs of this package, not to published paragraph-level numbers.
 """
 from __future__ import annotations
 
@@ -366,12 +375,19 @@ class DenseCaptionEvaluator:
     proposal_recall=True: .evaluate() also fills AUC and AR@AN, one entry per tIoU, .recall_curve (T, points) and
     .proposals_per_video (points,): proposal_recall below with its defaults, which see for the definition.  The mean of AUC
     over the tIoUs is comparable to ActivityNet's proposal figure only with its ten thresholds 0.5 .. 0.95 and one
-    annotation file; the tIoU is `tiou` with its + 1e-8."""
+    annotation file; the tIoU is `tiou` with its + 1e-8.
+    paragraph=True (and not only_proposals): .evaluate() also fills Para_Bleu_1..4, Para_METEOR, Para_ROUGE_L, Para_CIDEr
+    (a video's captions in time order read as one paragraph, scored per ground-truth file and averaged over the files) and
+    Para_RE_4, Para_XRE_4, Para_Div_1, Para_Div_2 (n-gram repetition, repetition across sentences and diversity of the
+    predicted paragraphs: paragraph_groups, paragraph_scores, paragraph_stats, paragraph_means), one
+    entry per tIoU, all equal, and .paragraph_per_video (video id -> {"stats": (4, 5) int32 total, distinct, in_repeated,
+    cross, max_count per n, "sentences", "tokens"}).  paragraph_top=k reads only the k best-scored proposals of a video
+    (by_proposal_score) as its paragraph; None reads all.  sort_references applies to the reference paragraphs too."""
 
     def __init__(self, ground_truth_filenames=None, prediction_filename=None, tious=None, max_proposals=1000,
                  prediction_fields=PREDICTION_FIELDS, verbose=False, only_proposals=False, *, device="cuda",
                  tokenizer: Callable[[str], List[str]] = tokenize, stemmer=None, synonyms=None, soda=False,
-                 sort_references=False, tiou_backend="host", proposal_recall=False):
+                 sort_references=False, tiou_backend="host", proposal_recall=False, paragraph=False, paragraph_top=None):
         if tious is None or len(tious) == 0:
             raise IOError("Please input a valid tIoU.")
         if not ground_truth_filenames:
@@ -392,6 +408,11 @@ class DenseCaptionEvaluator:
             raise ValueError(f"unknown tiou_backend {tiou_backend!r} ('host' or 'device')")
         self.tiou_backend, self.proposal_recall = tiou_backend, bool(proposal_recall)
         self.recall_curve = self.proposals_per_video = None
+        if paragraph_top is not None and (isinstance(paragraph_top, bool) or not isinstance(paragraph_top, (int, np.integer))
+                                          or paragraph_top < 1):
+            raise ValueError(f"paragraph_top {paragraph_top!r}: a positive integer or None expected")
+        self.paragraph, self.paragraph_top = bool(paragraph), None if paragraph_top is None else int(paragraph_top)
+        self.paragraph_per_video: Dict[str, dict] = {}
         self._tables = self._detection = self._table_tokens = None
         self.ground_truths = self.import_ground_truths(ground_truth_filenames)
         self.prediction = self.import_prediction(prediction_filename)
@@ -441,6 +462,8 @@ class DenseCaptionEvaluator:
                     self.scores.setdefault(metric, []).append(score)
             if self.soda:
                 self.scores.update(self.evaluate_soda())
+            if self.paragraph:
+                self.scores.update(self.evaluate_paragraph())
         if self.verbose:
             self.scores["Recall"], self.scores["Precision"] = [], []
             for t in self.tious:
@@ -526,6 +549,21 @@ class DenseCaptionEvaluator:
                 for m in SODA_METRICS:
                     print("Calculated tIoU: %1.1f, %s: %0.3f" % (t, m, out[m][k]))
         return out
+
+    def evaluate_paragraph(self) -> Dict[str, List[float]]:
+        """the Para_* keys, one entry per tIoU -- all equal: a paragraph does not depend on a
+        threshold -- and .paragraph_per_video"""
+        groups = paragraph_groups(self.ground_truths, self.prediction, self._tok, self.paragraph_top, self.sort_references)
+        out = paragraph_scores(groups, self.device, self.meteor_tables())
+        stats = paragraph_stats([groups.predicted[vid] for vid in groups.vids], self.device)
+        out.update(paragraph_means(stats))
+        self.paragraph_per_video = {
+            vid: {"stats": stats[v].copy(), "sentences": len(groups.predicted[vid]),
+                  "tokens": sum(map(len, groups.predicted[vid]))} for v, vid in enumerate(groups.vids)}
+        if self.verbose:
+            for m, score in out.items():
+                print("Calculated %s: %0.3f" % (m, score))
+        return {m: [score] * len(self.tious) for m, score in out.items()}
 
     def meteor_tables(self):
         """rewards.MeteorTables over the distinct hypothesis words of the submission (built at first use)"""
@@ -799,4 +837,118 @@ def soda_means(per_video: Dict[str, List[Tuple[float, float, float]]], T: int) -
             for triples in per_video.values():
                 total += triples[t][c]
             out[m].append(total / len(per_video))
+    return out
+
+
+# ---- paragraph evaluation
+class ParagraphGroups(NamedTuple):
+    """the host half of the paragraph evaluation: the ground-truth video ids (sorted), video id -> the predicted
+    paragraph (token tuples, one per kept sentence, in time order; [] when nothing is left), and per ground-truth file
+    video id -> the reference paragraph, for the videos that have one in that file"""
+    vids: List[str]
+    predicted: Dict[str, List[Tuple[str, ...]]]
+    references: List[Dict[str, List[Tuple[str, ...]]]]
+
+
+def _flat(sentences: Sequence[Sequence[str]]) -> Tuple[str, ...]:
+    return tuple(w for s in sentences for w in s)
+
+
+def paragraph_groups(ground_truths: Sequence[dict], prediction: Dict[str, list],
+                     tokenizer: Callable[[str], Sequence[str]] = tokenize, top: Optional[int] = None,
+                     sort_references: bool = False) -> ParagraphGroups:
+    """The paragraphs of a job (see ParagraphGroups) for every ground-truth video id; videos that only the prediction holds
+    are left out.  `prediction` is already cut to max_proposals per video.
+    Predicted paragraph: the `top` first positions of by_proposal_score (None: all), ordered by list index and then
+    stably by (start, end).  Reference paragraph of a file: its sentences of the video in file order, by (start, end) with
+    sort_references.  Every sentence passes remove_nonascii and the tokenizer; a sentence without a token is dropped, and
+    a file gives no reference paragraph for a video it lacks or of which no token is left.
+    A predicted paragraph past ops.REWARDS_MAX_L tokens or a reference paragraph past ops.REWARDS_MAX_R is a ValueError
+    naming the video (and the file): the scorers' limits, checked here, before anything goes to the device."""
+    from . import ops
+    clean = lambda sents: [t for t in (tuple(tokenizer(remove_nonascii(s))) for s in sents) if t]           # noqa: E731
+    vids = ground_truth_video_ids(ground_truths)
+    predicted: Dict[str, List[Tuple[str, ...]]] = {}
+    references: List[Dict[str, List[Tuple[str, ...]]]] = [{} for _ in ground_truths]
+    for vid in vids:
+        preds = prediction.get(vid, ())
+        kept = sorted(by_proposal_score(preds)[:top])
+        order = _by_time([preds[k]["timestamp"] for k in kept])
+        para = predicted[vid] = clean([preds[kept[o]]["sentence"] for o in order])
+        n = sum(map(len, para))
+        if n > ops.REWARDS_MAX_L:
+            raise ValueError(f"video {vid}: a predicted paragraph of {n} tokens; at most {ops.REWARDS_MAX_L} are supported "
+                             f"(paragraph_top=k reads only the k best-scored proposals)")
+        for f, gt in enumerate(ground_truths):
+            if vid not in gt:
+                continue
+            sents = gt[vid]["sentences"]
+            rorder = _by_time(gt[vid]["timestamps"]) if sort_references else range(len(sents))
+            ref = clean([sents[k] for k in rorder])
+            n = sum(map(len, ref))
+            if n > ops.REWARDS_MAX_R:
+                raise ValueError(f"video {vid}: a reference paragraph of {n} tokens in ground-truth file {f}; at most "
+                                 f"{ops.REWARDS_MAX_R} are supported (paragraph_top does not shorten a reference)")
+            if ref:
+                references[f][vid] = ref
+    return ParagraphGroups(vids, predicted, references)
+
+
+def paragraph_stats(paragraphs: Sequence[Sequence[Sequence[str]]], device="cuda") -> np.ndarray:
+    """(G, 4, 5) int32 numpy: total, distinct, in_repeated, cross, max_count of the n-grams, n = 1..4, of every paragraph
+    (a sequence of sentences, each a sequence of tokens; an empty sentence or paragraph is allowed): one ops.ngram_stats
+    launch over word ids of a rewards.StringTable of its own.  Predictions and references alike."""
+    import torch
+    from . import ops
+    from .rewards import StringTable
+    G = len(paragraphs)
+    if not G:
+        return np.zeros((0, 4, ops.NGRAM_STATS_INTS), dtype=np.int32)
+    table = StringTable()
+    tok, sent_off, para_off = [], [0], [0]
+    for g, para in enumerate(paragraphs):
+        start = len(tok)
+        for sent in para:
+            tok.extend(table.add(w) for w in sent)
+            sent_off.append(len(tok))
+        if len(tok) - start > ops.PARAGRAPH_MAX_TOKENS:
+            raise ValueError(f"paragraph {g} holds {len(tok) - start} tokens; at most {ops.PARAGRAPH_MAX_TOKENS} are supported")
+        para_off.append(len(sent_off) - 1)
+    dev = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int32)).to(device)                              # noqa: E731
+    return ops.ngram_stats(dev(tok), dev(sent_off), dev(para_off)).cpu().numpy()
+
+
+def paragraph_scores(groups: ParagraphGroups, device, tables) -> Dict[str, float]:
+    """Para_Bleu_1..4, Para_METEOR, Para_ROUGE_L, Para_CIDEr of a job: group f holds the pairs (predicted paragraph,
+    file f's reference paragraph) of the videos with a reference paragraph in f, in video order; all groups go through one
+    score_pairs call, so BLEU is corpus-level over a file, CIDEr's document frequencies are the file's reference
+    paragraphs, ROUGE-L and METEOR are means over the file's videos.  A video whose predicted paragraph is empty enters
+    as an empty hypothesis.  Each figure is the mean over the files with at least one pair, in file order; 0.0 without a
+    pair.  `tables`: a rewards.MeteorTables whose vocabulary holds every predicted word."""
+    hyps, refs, off = [], [], [0]
+    for refs_of in groups.references:
+        for vid in groups.vids:
+            if vid in refs_of:
+                hyps.append(_flat(groups.predicted[vid]))
+                refs.append(_flat(refs_of[vid]))
+        off.append(len(hyps))
+    out = {f"Para_{m}": 0.0 for m in METRICS}
+    if not hyps:
+        return out
+    per_file = score_pairs(hyps, refs, off, device, tables)
+    mine = [f for f in range(len(off) - 1) if off[f + 1] > off[f]]
+    for m in METRICS:
+        out[f"Para_{m}"] = sum(float(per_file[m][f]) for f in mine) / len(mine)
+    return out
+
+
+def paragraph_means(stats: np.ndarray) -> Dict[str, float]:
+    """Para_RE_4, Para_XRE_4, Para_Div_1, Para_Div_2 of the (V, 4, 5) integers of the videos' predicted paragraphs: per
+    video RE_n = (total - distinct) / total, XRE_n = cross / total, Div_n = distinct / total; each key is the mean over
+    the videos whose total at that n is > 0, in video order, 0.0 when there is none"""
+    out = {}
+    for key, n, value in (("Para_RE_4", 4, lambda r: (r[0] - r[1]) / r[0]), ("Para_XRE_4", 4, lambda r: r[3] / r[0]),
+                          ("Para_Div_1", 1, lambda r: r[1] / r[0]), ("Para_Div_2", 2, lambda r: r[1] / r[0])):
+        vals = [value([int(x) for x in row]) for row in stats[:, n - 1] if row[0] > 0]
+        out[key] = sum(vals) / len(vals) if vals else 0.0
     return out

@@ -870,6 +870,30 @@ def caption_eval(hyp, hyp_len, ref, ref_len, group_off):
     return pair_ints, pair_lcs, pair_cider, group_scores
 
 
+# ---- paragraph n-gram statistics (csrc/paragraph.hip)
+PARAGRAPH_MAX_TOKENS, NGRAM_STATS_INTS = 1024, 5             # BMHRL_PARAGRAPH_MAX_TOKENS / BMHRL_NGRAM_STATS_INTS
+
+
+def ngram_stats(tok, sent_off, para_off):
+    """(G, 4, 5) int32: total, distinct, in_repeated, cross, max_count of the n-grams, n = 1..4, of G paragraphs; see
+    bmhrl_ngram_stats in include/bmhrl_hip.h.  tok (n_tok) int32 word ids, sent_off (S + 1) int32 token offsets of the
+    sentences, para_off (G + 1) int32 sentence offsets of the paragraphs, all contiguous and on one device.  A paragraph
+    holds at most PARAGRAPH_MAX_TOKENS tokens.  Synchronises the stream once (the offsets are checked on the host); not for
+    captured graphs."""
+    for t in (tok, sent_off, para_off):
+        if t.dtype != torch.int32:
+            raise ValueError("ngram_stats: int32 tensors expected")
+    if tok.dim() != 1 or sent_off.dim() != 1 or para_off.dim() != 1 or not (tok.is_contiguous() and sent_off.is_contiguous()
+                                                                            and para_off.is_contiguous()):
+        raise ValueError("ngram_stats: tok (n_tok), sent_off (S + 1) and para_off (G + 1), contiguous, expected")
+    if sent_off.numel() < 1 or para_off.numel() < 1:
+        raise ValueError("ngram_stats: sent_off (S + 1) and para_off (G + 1) hold at least one offset")
+    S, G = sent_off.numel() - 1, para_off.numel() - 1
+    stats = torch.empty(G, 4, NGRAM_STATS_INTS, dtype=torch.int32, device=sent_off.device)
+    _launch("bmhrl_ngram_stats", tok, tok.numel(), sent_off, S, para_off, G, stats)
+    return stats
+
+
 # ---- SODA_c: the all-pairs METEOR matrix and the ordered assignment (csrc/soda.hip)
 SODA_MAX_REFS, SODA_MAX_T = 256, 16          # BMHRL_SODA_MAX_REFS / _T of include/bmhrl_hip.h
 

@@ -1054,6 +1054,28 @@ int bmhrl_policy_loss_bwd(const float* logp, int64_t ld, const int64_t* action, 
                           const float* ent_weight, const float* gscale, const float* drow, float* dlogp, int64_t ldg, int64_t rows,
                           int32_t V, bmhrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Paragraph n-gram statistics (bmhrl_amd/evaluate.py paragraph_stats; the rules are in DESIGN.md section 33).  A paragraph
+ * is a run of sentences, a sentence a run of word ids: tok (n_tok) int32 (any value: only equality is used), sent_off
+ * (S + 1) int32 token offsets of the sentences (sent_off[0] = 0, sent_off[S] = n_tok), para_off (G + 1) int32 sentence
+ * offsets of the paragraphs (para_off[0] = 0, para_off[G] = S); both never descend, and an empty sentence or paragraph is
+ * allowed.  All three are device memory.
+ *  S1. For n = 1..4 an occurrence is a start position whose n tokens lie inside one sentence; two occurrences are the same
+ *      gram when their n ids are equal.  Grams span neither a sentence nor a paragraph boundary.
+ *  S2. stats (G, 4, BMHRL_NGRAM_STATS_INTS) int32, per paragraph and n: total (occurrences), distinct (different grams),
+ *      in_repeated (occurrences whose gram occurs at least twice in the paragraph), cross (occurrences whose gram also
+ *      occurs in an earlier sentence of the paragraph), max_count (the largest multiplicity; 0 when total = 0).
+ *  S3. A paragraph holds at most BMHRL_PARAGRAPH_MAX_TOKENS tokens; any number of sentences.
+ *  Refused with -22 before the launch, stats untouched: a null pointer (tok may be null only with n_tok = 0), G <= 0,
+ *  S < 0, n_tok < 0, offsets that descend or do not span [0, S] / [0, n_tok], a paragraph past the limit.  The offsets are
+ *  copied back and checked on the host as bmhrl_caption_eval does it: one stream synchronisation, not for captured graphs.
+ *  One 256-thread workgroup per paragraph, integers only, no atomics: equal inputs give equal bits.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_PARAGRAPH_MAX_TOKENS 1024
+#define BMHRL_NGRAM_STATS_INTS 5
+int bmhrl_ngram_stats(const int32_t* tok, int32_t n_tok, const int32_t* sent_off, int32_t S, const int32_t* para_off,
+                      int32_t G, int32_t* stats, bmhrl_stream_t stream);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
