@@ -146,6 +146,7 @@ PROTOTYPES = {
     "bmhrl_soda_dp": [ptr, i32, ptr, i32, ptr, ptr, ptr, i32, ptr, i64, ptr, i32, ptr, ptr],
     "bmhrl_sample_step": [ptr, i64, i32, i32, f32, i32, f32, u64, ptr, ptr, i64, i32, i32, ptr, ptr, ptr, i64, ptr, ptr, ptr, ptr],
     "bmhrl_logit_rules": [ptr, i64, i32, i32, ptr, i64, ptr, i32, i32, f32, i32, i32, ptr],
+    "bmhrl_logit_rules_ctx": [ptr, i64, i32, i32, ptr, i64, ptr, i32, i32, f32, i32, i32, ptr, i64, i32, i32, f32, ptr],
     "bmhrl_consensus": [ptr, i64, i32, i32, i32, i64, i32, ptr, i32, ptr, ptr, ptr],
     "bmhrl_word_cost": [ptr, i64, ptr, i64, i64, f32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr],
     "bmhrl_lsa_match": [ptr, i64, i64, i64, ptr, i32, i32, i32, ptr, ptr],

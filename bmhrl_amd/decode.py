@@ -16,6 +16,8 @@ sample_decode / sample_decoder: temperature / top-k / top-p sampling, n samples 
 (SampleDecoder), or over full re-runs.
 Every decoder takes no_repeat_ngram / min_len / repetition_penalty (the constraints section): the rules edit the step's
 log-probs before the choice, in the captured step through one HIP launch.
+Every decoder takes context / context_ngram / context_penalty (the context rules C1-C5 of the same section): the tokens of
+a video's earlier captions, whose n-grams are banned and whose words are penalised, through the same one launch.
 beam_decode / sample_decode take select="consensus" (the consensus section): the returned caption is the hypothesis that
 agrees most with the clip's other hypotheses, one HIP launch after the token loop.
 beam_decode takes beam_groups / diversity_penalty (the group beam search section): diverse beam search, the beams in groups
@@ -34,21 +36,25 @@ _BF16 = torch.bfloat16
 
 
 def greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, return_first=False, memoise=True,
-                  incremental=None, no_repeat_ngram=0, min_len=0, repetition_penalty=1.0):
+                  incremental=None, no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, context=None, context_ngram=0,
+                  context_penalty=1.0):
     """memoise=True (default) runs the encoder and the fusion layers' memory projections once per clip batch instead of
     once per generated token; the tokens and log-probs are the same as with the reference's full re-run (memoise=False).
     incremental (default: on for the HIP agent in eval mode on a GPU with both modalities) additionally decodes through
     IncrementalDecoder.  Models without encode_memory() (anything but the HIP BMHrlAgent) always take the full re-run.
     no_repeat_ngram / min_len / repetition_penalty: the constraints section's rules, on every path; with a rule set,
     return_first returns the first step's adjusted log-probs, and a max_len + 1 above ops.LOGIT_RULES_MAX_HIST (256, the
-    kernel's history capacity) takes the re-run path."""
+    kernel's history capacity) takes the re-run path.
+    context / context_ngram / context_penalty: the context rules C1-C5 of that section -- context is a (B, C <= 1024) int64
+    tensor or a list of B integer lists, per clip the tokens of the video's earlier captions."""
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty, max_len)
     with torch.no_grad():
         B = feature_stacks['audio'].shape[0]
         device = feature_stacks['audio'].device
+        context = _context(context, context_ngram, context_penalty, B, pad_idx, device)
         memoise = memoise and hasattr(model, "encode_memory") and not model.training
         dec = _incremental(IncrementalDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx,
-                           incremental=incremental if memoise else False, rules=rules)
+                           incremental=incremental if memoise else False, rules=rules, context=context)
         if dec is not None:
             return dec.run(return_first)
         done = torch.zeros(B, 1, dtype=torch.bool, device=device)
@@ -64,7 +70,10 @@ def greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, m
                 last = model.inference_from_memory(memory, trg, masks, kv_cache)[:, -1]
             else:
                 last = _rerun_logp(model, x, rep, trg, modality, pad_idx)
-            if rules is not None:
+            if context is not None:
+                last = _apply_context_rules(last.float(), trg, trg.size(-1) - 1, rules, end_idx, pad_idx, context[0], 1,
+                                            context[1])
+            elif rules is not None:
                 last = _apply_rules(last.float(), trg, trg.size(-1) - 1, *rules, end_idx, pad_idx)
             if first is None:
                 first = last.clone()
@@ -75,21 +84,26 @@ def greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, m
 
 
 def _incremental(cls, model, fs, modality, max_len, start_idx, end_idx, pad_idx, rows=1, incremental=None, params=None,
-                 rules=None):
+                 rules=None, context=None):
     """the decoder of class `cls` (`rows` rows per clip) with the clip batch begun, or None: take the re-run path.
     incremental=None: the class's `enabled`; params: SampleDecoder.set_params arguments, rules: what _rule_args returned
-    (IncrementalDecoder.set_rules arguments, None: all off), both set before begin()"""
+    (IncrementalDecoder.set_rules arguments, None: all off), context: what _context returned (the clips' contexts and
+    the set_context_rules arguments, None: off), all set before begin()"""
     if incremental is None:
         incremental = cls.enabled
     if not (incremental and hasattr(model, "encode_memory") and not model.training and fs['audio'].device.type == "cuda"
             and modality == "audio_video" and max_len >= 1 and cls._fits(model, rows)):
         return None
-    if rules is not None and max_len + 1 > ops.LOGIT_RULES_MAX_HIST:
+    if (rules is not None or context is not None) and max_len + 1 > ops.LOGIT_RULES_MAX_HIST:
+        return None
+    if context is not None and getattr(model, "voc_size", 0) > ops.LOGIT_RULES_CTX_MAX_V:
         return None
     dec = cls.for_batch(model, fs, max_len, start_idx, end_idx, pad_idx, rows)
     if params is not None:
         dec.set_params(*params)
     dec.set_rules(*(rules or _NO_RULES))
+    dec.set_context_rules(*(context[1] if context is not None else _NO_CONTEXT_RULES))
+    dec.set_context(context[0] if context is not None else None)
     return dec if dec.begin(fs) else None
 
 
@@ -110,15 +124,19 @@ def bimodal_decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
     return greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality)
 
 
-def greedy_decoder(no_repeat_ngram=0, min_len=0, repetition_penalty=1.0):
+def greedy_decoder(no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, context_ngram=0, context_penalty=1.0):
     """a greedy decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality)
     under the constraints section's rules, e.g. validation_1by1_loop(cfg, model, loader, greedy_decoder(3, min_len=5), epoch,
-    TBoard)"""
+    TBoard).  context_ngram / context_penalty: the context rules, for the clips' contexts that a caller such as
+    predict.caption_segments(paragraph=True) hands over with the optional keyword context=; without it the call is the
+    reference's."""
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty) or _NO_RULES
+    crules = _context_args(context_ngram, context_penalty) or _NO_CONTEXT_RULES
 
-    def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
+    def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, context=None):
         return greedy_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, no_repeat_ngram=rules[0],
-                             min_len=rules[1], repetition_penalty=rules[2])
+                             min_len=rules[1], repetition_penalty=rules[2], context=context, context_ngram=crules[0],
+                             context_penalty=crules[1])
     return decoder
 
 
@@ -220,6 +238,9 @@ class IncrementalDecoder:
         self._shadow_sig = None
         self.steps_run = 0
         self.rules = None               # set_rules: (no_repeat_ngram, min_len, repetition_penalty) while a rule is set
+        self.ctx_rules = None           # set_context_rules: (context_ngram, context_penalty) while one is set
+        self.has_context = False        # set_context: do the rows of self.ctx hold the clips' contexts?
+        self.ctx = torch.full((B, ops.LOGIT_RULES_MAX_CTX), pad_idx, dtype=torch.int64, device=dev)
         self._init_search()
         with torch.no_grad():
             self._reset()
@@ -249,12 +270,61 @@ class IncrementalDecoder:
                     self._constrain()
                 self._capture()
 
+    def _context_on(self):
+        """does the token step run the context rules?  Only with a rule set AND a context present (rule C4)"""
+        return self.ctx_rules is not None and self.has_context
+
+    def set_context_rules(self, context_ngram=0, context_penalty=1.0):
+        """the context rules C1-C2 for the decodes that follow: launch arguments as set_rules' are, so the step is captured
+        again when they change while a context is present.  Not while a clip batch is being decoded; they stay on the
+        decoder as set_rules' do, and _incremental sets them before every clip batch, the defaults included."""
+        crules = _context_args(context_ngram, context_penalty)
+        if crules is not None and self.max_len + 1 > ops.LOGIT_RULES_MAX_HIST:
+            raise ValueError(f"set_context_rules: a history of {self.max_len + 1} tokens exceeds {ops.LOGIT_RULES_MAX_HIST}")
+        if crules is not None and self.logp.shape[-1] > ops.LOGIT_RULES_CTX_MAX_V:
+            raise ValueError(f"set_context_rules: a vocabulary of {self.logp.shape[-1]} exceeds {ops.LOGIT_RULES_CTX_MAX_V}")
+        if crules != self.ctx_rules:
+            was = self._context_on()
+            self.ctx_rules = crules
+            self._context_changed(was, True)
+
+    def set_context(self, context=None):
+        """the clips' contexts (B, C <= LOGIT_RULES_MAX_CTX) int64 for the decodes that follow, or None: copied into the
+        static (B, LOGIT_RULES_MAX_CTX) buffer the captured step reads, the rest filled with pad_idx, so a new context
+        needs no capture; the step is captured again only when a context appears or goes while context rules are set
+        (another launch: bmhrl_logit_rules_ctx in place of the plain one, or of none)."""
+        was = self._context_on()
+        if context is None:
+            self.has_context = False
+        else:
+            if context.dim() != 2 or context.shape[0] != self.B or context.shape[1] > ops.LOGIT_RULES_MAX_CTX:
+                raise ValueError(f"set_context: a ({self.B}, C <= {ops.LOGIT_RULES_MAX_CTX}) tensor expected, got "
+                                 f"{tuple(context.shape)}")
+            self.ctx.fill_(self.pad_idx)
+            self.ctx[:, :context.shape[1]] = context
+            self.has_context = True
+        self._context_changed(was, False)
+
+    def _context_changed(self, was, new_rules):
+        now = self._context_on()
+        if (now != was or (now and new_rules)) and self.graph is not None:
+            if now or self.rules is not None:
+                # eager once, as in set_rules: the kernel's first launch is not one under capture
+                self._constrain()
+            self._capture()
+
     def _constrain(self):
-        """rules 1-3 on self.logp, rows' sequences from self.out.  An end_idx that is no token id (callers that never stop)
-        leaves rule 3 nothing to ban."""
-        n, m, theta = self.rules
+        """rules 1-3 on self.logp, rows' sequences from self.out -- with context rules set and a context present, rules
+        1, C1, 2, C2, 3 through the one launch that replaces the plain one.  An end_idx that is no token id (callers that
+        never stop) leaves rule 3 nothing to ban."""
+        n, m, theta = self.rules or _NO_RULES
         V = self.logp.shape[-1]
         ends = 0 <= self.end_idx < V
+        if self._context_on():
+            ops.logit_rules_ctx(self.logp, V, self.R, V, self.out, self.t, n, m if ends else 0, theta,
+                                self.end_idx if ends else self.pad_idx, self.pad_idx, self.ctx, self.R // self.B,
+                                *self.ctx_rules)
+            return
         ops.logit_rules(self.logp, V, self.R, V, self.out, self.t, n, m if ends else 0, theta,
                         self.end_idx if ends else self.pad_idx, self.pad_idx)
 
@@ -461,7 +531,7 @@ class IncrementalDecoder:
         logp = WorkerHeadFn.apply(w_feat.view(B, 1, -1), gc.view(B, 1, -1), ag.worker.core.projection.weight,
                                   ag.worker.core.projection.bias)
         self.logp.copy_(logp)
-        if self.rules is not None:
+        if self.rules is not None or self._context_on():
             self._constrain()
             logp = self.logp
         self._choose(logp)
@@ -494,8 +564,32 @@ class IncrementalDecoder:
 #     Finished rows are adjusted like live ones; their choice ignores lp already.
 # A token id of s outside [0, V) takes part in the comparisons of rule 2 but selects no entry of lp.
 # Refused with ValueError: n < 0, m < 0, n or m not an integer, theta non-finite or <= 0, m > max_len.
+#
+# Context rules (paragraph-aware decoding; both paths -- bmhrl_logit_rules_ctx in the captured token step,
+# _apply_context_rules in the re-runs -- implement exactly these).  Inputs: context_ngram = n_c >= 0, context_penalty =
+# theta_c (finite, > 0; the fp32 value of the host float), and per clip a context ctx of C <= 1024 int64 entries
+# (ops.LOGIT_RULES_MAX_CTX): the tokens of the video's earlier captions.  An entry is a WORD when 0 <= id < V and
+# id != pad_idx; anything else is a GAP -- a sentence separator or filler.  All rows of a clip (beams, samples) share the
+# clip's context.
+#  C1. penalty.  theta_c != 1: for every distinct word id v of the context, lp[v] = lp[v] * theta_c -- one fp32 multiply,
+#      once per id however often it occurs.  It is applied after rule 1: an id that is both in s and in the context takes
+#      rule 1's multiply first and then this one.  The order is fixed, so the bits are too;
+#  C2. ban.  n_c >= 1 and t >= n_c - 1: the tail is s[t-n_c+2 .. t], the last n_c - 1 GENERATED tokens -- s[0], the start
+#      token, is never part of it; for n_c = 1 the tail is empty.  For every j in [0, C - n_c] such that ctx[j .. j+n_c-1]
+#      are all words and ctx[j .. j+n_c-2] equals the tail, lp[ctx[j+n_c-1]] = -inf.  A window that holds a gap matches
+#      nothing, so n-grams never span two context sentences;
+#  C3. order.  The rules run as 1, C1, 2, C2, 3: bans come after penalties, so a banned entry is -inf whatever was
+#      multiplied into it.  Rule 4 (no renormalising; everything downstream reads the adjusted values) holds unchanged;
+#  C4. off state.  With no context given, or with n_c = 0 and theta_c = 1, nothing of these rules runs and the step has
+#      the launches it has without them: the plain bmhrl_logit_rules when rules 1-3 are set, none otherwise.  With them,
+#      bmhrl_logit_rules_ctx REPLACES the plain launch: still one rules launch per token;
+#  C5. refused with ValueError: n_c < 0 or not an integer, theta_c non-finite or <= 0, a context with more than 1024
+#      columns, a context whose row count is not the clip count.
+# The ban guarantees that no returned hypothesis shares an n_c-gram with the sentences of its context, and nothing more.
+# A vocabulary above ops.LOGIT_RULES_CTX_MAX_V (65536, the kernel's bit map) takes the re-run path.
 
 _NO_RULES = (0, 0, 1.0)
+_NO_CONTEXT_RULES = (0, 1.0)
 
 
 def _rule_args(no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, max_len=None):
@@ -540,6 +634,74 @@ def _apply_rules(lp, hist, t, ngram, min_len, penalty, end_idx, pad_idx):
     return lp
 
 
+def _context_args(context_ngram=0, context_penalty=1.0):
+    """(n_c, theta_c as the fp32 value the kernel sees) of valid arguments, None when they are the defaults (rule C4)"""
+    try:
+        whole = not isinstance(context_ngram, bool) and int(context_ngram) == context_ngram
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or int(context_ngram) < 0:
+        raise ValueError(f"context_ngram must be an integer >= 0, got {context_ngram!r}")
+    try:
+        theta = float(context_penalty)
+    except (TypeError, ValueError):
+        raise ValueError(f"context_penalty must be finite and > 0, got {context_penalty!r}") from None
+    if not (math.isfinite(theta) and theta > 0 and math.isfinite(_f32(theta)) and _f32(theta) > 0):
+        raise ValueError(f"context_penalty must be finite and > 0, got {context_penalty}")
+    crules = (int(context_ngram), _f32(theta))
+    return None if crules == _NO_CONTEXT_RULES else crules
+
+
+def _context(context, context_ngram, context_penalty, B, pad_idx, device):
+    """the checked arguments of the context rules: ((B, C) int64 contexts on `device`, (n_c, theta_c)), or None in the
+    off state of rule C4 (no context, or n_c = 0 and theta_c = 1).  context: a (B, C <= 1024) integer tensor, or B integer
+    lists that are padded to a common width (at least 1) with pad_idx."""
+    crules = _context_args(context_ngram, context_penalty)
+    if context is None:
+        return None
+    if torch.is_tensor(context):
+        if context.dim() != 2 or context.is_floating_point() or context.dtype == torch.bool:
+            raise ValueError(f"context must be a (B, C) integer tensor, got {tuple(context.shape)} {context.dtype}")
+        ctx = context
+    else:
+        rows = [[int(v) for v in row] for row in context]
+        width = max([1] + [len(row) for row in rows])
+        ctx = torch.tensor([row + [pad_idx] * (width - len(row)) for row in rows], dtype=torch.int64).view(len(rows), width)
+    if ctx.shape[0] != B:
+        raise ValueError(f"context holds {ctx.shape[0]} rows for {B} clips")
+    if ctx.shape[1] > ops.LOGIT_RULES_MAX_CTX:
+        raise ValueError(f"a context of {ctx.shape[1]} columns exceeds {ops.LOGIT_RULES_MAX_CTX}")
+    if crules is None:
+        return None
+    if ctx.shape[1] == 0:
+        ctx = torch.full((B, 1), pad_idx, dtype=torch.int64)
+    return ctx.to(device=device, dtype=torch.int64).contiguous(), crules
+
+
+def _apply_context_rules(lp, hist, t, rules, end_idx, pad_idx, ctx, rows_per_ctx, crules):
+    """rules 1, C1, 2, C2, 3 (rule C3's order) in fp32 torch ops: lp (R, V) fp32 log-probs, hist (R, >= t + 1) int64
+    sequences, rules = (n, m, theta) or None, ctx (R / rows_per_ctx, C) int64 contexts, crules = (n_c, theta_c) -> the
+    adjusted (R, V)"""
+    R, V = lp.shape
+    n, m, theta = rules or _NO_RULES
+    n_c, theta_c = crules
+    c = ctx.to(hist.device).repeat_interleave(rows_per_ctx, 0)
+    word = (c >= 0) & (c < V) & (c != pad_idx)
+    idx = c.clamp(0, V - 1)
+    lp = _apply_rules(lp, hist, t, 0, 0, theta, end_idx, pad_idx)                                   # rule 1
+    if theta_c != 1:
+        seen = torch.zeros(R, V, dtype=torch.int32, device=lp.device).scatter_add_(1, idx, word.to(torch.int32)) > 0
+        lp = torch.where(seen, lp * torch.tensor(theta_c, dtype=lp.dtype, device=lp.device), lp)
+    lp = _apply_rules(lp, hist, t, n, 0, 1.0, end_idx, pad_idx)                                     # rule 2
+    if n_c >= 1 and t >= n_c - 1 and c.shape[1] >= n_c:
+        tail = hist[:, t + 2 - n_c:t + 1]                                                           # (R, n_c - 1)
+        match = (c.unfold(1, n_c, 1)[..., :n_c - 1] == tail.unsqueeze(1)).all(-1) & word.unfold(1, n_c, 1).all(-1)
+        banned = torch.zeros(R, V, dtype=torch.int32, device=lp.device).scatter_add_(
+            1, idx[:, n_c - 1:], match.to(torch.int32)) > 0
+        lp = torch.where(banned, torch.full_like(lp, float("-inf")), lp)
+    return _apply_rules(lp, hist, t, 0, m, 1.0, end_idx, pad_idx)                                   # rule 3
+
+
 # ---------------------------------------------------------------------------------------------------------- beam search
 # Rules (both paths below implement exactly these):
 #  1. beam 0 of a sample starts live with score 0 and input start_idx; beams 1..K-1 start finished with score -inf;
@@ -558,7 +720,7 @@ def _apply_rules(lp, hist, t, ngram, min_len, penalty, end_idx, pad_idx):
 def beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, beam_size=4, length_penalty=0.0,
                 return_scores=False, return_beams=False, incremental=None, no_repeat_ngram=0, min_len=0,
                 repetition_penalty=1.0, select="logp", consensus_n=4, consensus_weight=None, beam_groups=1,
-                diversity_penalty=0.0, return_groups=False):
+                diversity_penalty=0.0, return_groups=False, context=None, context_ngram=0, context_penalty=1.0):
     """Beam search with the reference decoder's arguments.  Returns tokens (B, n + 1) int64, then -- when asked -- the
     chosen hypotheses' raw scores (B,) fp32, then all K hypotheses sorted best first as tokens (B, K, m + 1) (m: the
     longest n_k of all of them, so that no hypothesis is cut) and raw scores (B, K).
@@ -575,7 +737,9 @@ def beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, mod
     of K / G that choose one after another, through GroupBeamDecoder under the conditions BeamDecoder is taken, else over
     re-runs.  With G = 1 (the default) the search is the plain one above whatever diversity_penalty is.  return_groups (only
     with return_beams) appends the group index (B, K) int64 of the returned hypotheses, in their order, after the beams'
-    scores and before the consensus utilities."""
+    scores and before the consensus utilities.
+    context / context_ngram / context_penalty: the context rules C1-C5 of the constraints section; the K beams of a clip
+    share the clip's context."""
     K = int(beam_size)
     if K < 1:
         raise ValueError(f"beam_size must be >= 1, got {beam_size}")
@@ -583,44 +747,50 @@ def beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, mod
     consensus = _consensus_args(select, consensus_n, consensus_weight)
     G, lam = _group_args(K, beam_groups, diversity_penalty, return_groups, return_beams)
     with torch.no_grad():
+        context = _context(context, context_ngram, context_penalty, feature_stacks['audio'].shape[0], pad_idx,
+                           feature_stacks['audio'].device)
         if G == 1:
             dec = _incremental(BeamDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, K,
-                               incremental, rules=rules)
+                               incremental, rules=rules, context=context)
             found = dec.run() if dec is not None else _beam_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
-                                                                  modality, K, rules)
+                                                                  modality, K, rules, context)
         else:
             dec = _incremental(GroupBeamDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, K,
-                               incremental, params=(G, lam), rules=rules)
+                               incremental, params=(G, lam), rules=rules, context=context)
             found = dec.run() if dec is not None else _group_beam_rerun(model, feature_stacks, max_len, start_idx, end_idx,
-                                                                        pad_idx, modality, K, G, lam, rules)
+                                                                        pad_idx, modality, K, G, lam, rules, context=context)
         util = None if consensus is None else _consensus_utilities(dec, found[0], found[2], end_idx, *consensus)
         return _beam_result(*found, end_idx, length_penalty, return_scores, return_beams, util,
                             K // G if return_groups else None)
 
 
 def beam_decoder(beam_size=4, length_penalty=0.0, no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, select="logp",
-                 consensus_n=4, consensus_weight=None, beam_groups=1, diversity_penalty=0.0):
+                 consensus_n=4, consensus_weight=None, beam_groups=1, diversity_penalty=0.0, context_ngram=0,
+                 context_penalty=1.0):
     """a decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality), e.g.
     validation_1by1_loop(cfg, model, loader, beam_decoder(4), epoch, TBoard); select / consensus_n / consensus_weight: the
     consensus section's choice among the K beams; beam_groups / diversity_penalty: the group beam search section's diverse
-    beams, e.g. beam_decoder(8, beam_groups=4, diversity_penalty=0.5, select="consensus")"""
+    beams, e.g. beam_decoder(8, beam_groups=4, diversity_penalty=0.5, select="consensus"); context_ngram / context_penalty:
+    the context rules, for the contexts handed over with the optional keyword context= (as greedy_decoder)"""
     if int(beam_size) < 1:
         raise ValueError(f"beam_size must be >= 1, got {beam_size}")
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty) or _NO_RULES
     _consensus_args(select, consensus_n, consensus_weight)
     _group_args(int(beam_size), beam_groups, diversity_penalty)
+    crules = _context_args(context_ngram, context_penalty) or _NO_CONTEXT_RULES
 
-    def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
+    def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, context=None):
         return beam_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, beam_size=beam_size,
                            length_penalty=length_penalty, no_repeat_ngram=rules[0], min_len=rules[1],
                            repetition_penalty=rules[2], select=select, consensus_n=consensus_n,
-                           consensus_weight=consensus_weight, beam_groups=beam_groups, diversity_penalty=diversity_penalty)
+                           consensus_weight=consensus_weight, beam_groups=beam_groups, diversity_penalty=diversity_penalty,
+                           context=context, context_ngram=crules[0], context_penalty=crules[1])
     return decoder
 
 
-def _beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K, rules=None):
+def _beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K, rules=None, context=None):
     """rules 1-4 over full re-runs of model.inference on the prefix batch -> (tokens (B, K, n + 1), scores (B, K), n);
-    rules: what _rule_args returned"""
+    rules: what _rule_args returned, context: what _context returned"""
     B = fs['audio'].shape[0]
     dev = fs['audio'].device
     rep, x = _rerun_setup(fs, K)
@@ -632,7 +802,9 @@ def _beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K, ru
     steps = 0
     while steps < max_len:
         lp = _rerun_logp(model, x, rep, hist, modality, pad_idx)
-        if rules is not None:
+        if context is not None:
+            lp = _apply_context_rules(lp, hist, steps, rules, end_idx, pad_idx, context[0], K, context[1])
+        elif rules is not None:
             lp = _apply_rules(lp, hist, steps, *rules, end_idx, pad_idx)
         V = lp.shape[-1]
         cand = scores.unsqueeze(-1) + lp.view(B, K, V)
@@ -814,9 +986,10 @@ def _group_args(K, beam_groups=1, diversity_penalty=0.0, return_groups=False, re
     return G, _f32(lam)
 
 
-def _group_beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K, G, penalty, rules=None, trace=None):
+def _group_beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, K, G, penalty, rules=None, trace=None,
+                      context=None):
     """rules G1-G4 and beam rule 4 over full re-runs of model.inference on the prefix batch -> (tokens (B, K, n + 1),
-    scores (B, K), n); rules: what _rule_args returned.  trace: a list that receives one dict per step -- the step's log-probs
+    scores (B, K), n); rules: what _rule_args returned, context: what _context returned.  trace: a list that receives one dict per step -- the step's log-probs
     `logp` (B, K, V), the `scores` / `finished` it started from and, after it, `parent`, `tok`, `new_scores`, `new_finished`
     (B, K) and the beams `hist` (B, K, step + 2)."""
     B = fs['audio'].shape[0]
@@ -832,7 +1005,9 @@ def _group_beam_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality,
     steps = 0
     while steps < max_len:
         lp = _rerun_logp(model, x, rep, hist, modality, pad_idx)
-        if rules is not None:
+        if context is not None:
+            lp = _apply_context_rules(lp, hist, steps, rules, end_idx, pad_idx, context[0], K, context[1])
+        elif rules is not None:
             lp = _apply_rules(lp, hist, steps, *rules, end_idx, pad_idx)
         V = lp.shape[-1]
         cand = scores.unsqueeze(-1) + lp.view(B, K, V)
@@ -969,7 +1144,8 @@ def _f32(x):
 
 def sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, n=1, temperature=1.0, top_k=0,
                   top_p=1.0, seed=None, length_penalty=0.0, return_samples=False, incremental=None, no_repeat_ngram=0,
-                  min_len=0, repetition_penalty=1.0, select="logp", consensus_n=4, consensus_weight=None):
+                  min_len=0, repetition_penalty=1.0, select="logp", consensus_n=4, consensus_weight=None, context=None,
+                  context_ngram=0, context_penalty=1.0):
     """Sampled decoding with the reference decoder's arguments (rules above).  Returns tokens (B, m + 1) int64 (rule 7), then
     -- with return_samples -- all samples (B, n, m' + 1), their sum_logp (B, n) fp32 and the per-step model / sampling
     log-probs (B, n, m') fp32 (m': the steps of rule 6; zeros after a row's end).  seed=None draws one from `random`.
@@ -980,16 +1156,21 @@ def sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, m
     select="consensus" (with consensus_n = N in [1, 4] and consensus_weight = None or a (V,) tensor of token weights)
     replaces rule 7's choice by the consensus section's: the returned tokens are the sample with the largest utility, and
     return_samples appends the samples' utilities (B, n) fp64, in the samples' order, as the LAST (sixth) element of the
-    tuple.  With select="logp" (the default) the tuple is as described above."""
+    tuple.  With select="logp" (the default) the tuple is as described above.
+    context / context_ngram / context_penalty: the context rules C1-C5 of the constraints section; the n samples of a clip
+    share the clip's context."""
     n, temperature, top_k, top_p = _sample_args(n, temperature, top_k, top_p)
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty, max_len)
     consensus = _consensus_args(select, consensus_n, consensus_weight)
     seed = random.getrandbits(62) if seed is None else int(seed) % _U64
     with torch.no_grad():
+        context = _context(context, context_ngram, context_penalty, feature_stacks['audio'].shape[0], pad_idx,
+                           feature_stacks['audio'].device)
         dec = _incremental(SampleDecoder, model, feature_stacks, modality, max_len, start_idx, end_idx, pad_idx, n, incremental,
-                           params=(temperature, top_k, top_p), rules=rules)
+                           params=(temperature, top_k, top_p), rules=rules, context=context)
         found = dec.run(seed) if dec is not None else _sample_rerun(model, feature_stacks, max_len, start_idx, end_idx, pad_idx,
-                                                                    modality, n, temperature, top_k, top_p, seed, rules)
+                                                                    modality, n, temperature, top_k, top_p, seed, rules,
+                                                                    context)
         if consensus is None:
             return _sample_result(*found, end_idx, length_penalty, return_samples)
         util = _consensus_utilities(dec, found[0], found[4], end_idx, *consensus)
@@ -997,20 +1178,24 @@ def sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, m
 
 
 def sample_decoder(n=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
-                   repetition_penalty=1.0, select="logp", consensus_n=4, consensus_weight=None):
+                   repetition_penalty=1.0, select="logp", consensus_n=4, consensus_weight=None, context_ngram=0,
+                   context_penalty=1.0):
     """a decoder with the reference's signature (model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality), e.g.
     validation_1by1_loop(cfg, model, loader, sample_decoder(4, top_p=0.9), epoch, TBoard); seed=None: a fresh seed per call;
     select / consensus_n / consensus_weight: the consensus section's choice among the n samples, e.g.
-    sample_decoder(8, top_p=0.9, select="consensus")"""
+    sample_decoder(8, top_p=0.9, select="consensus"); context_ngram / context_penalty: the context rules, for the contexts
+    handed over with the optional keyword context= (as greedy_decoder)"""
     n, temperature, top_k, top_p = _sample_args(n, temperature, top_k, top_p)
     rules = _rule_args(no_repeat_ngram, min_len, repetition_penalty) or _NO_RULES
     _consensus_args(select, consensus_n, consensus_weight)
+    crules = _context_args(context_ngram, context_penalty) or _NO_CONTEXT_RULES
 
-    def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality):
+    def decoder(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, context=None):
         return sample_decode(model, feature_stacks, max_len, start_idx, end_idx, pad_idx, modality, n=n,
                              temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, length_penalty=length_penalty,
                              no_repeat_ngram=rules[0], min_len=rules[1], repetition_penalty=rules[2], select=select,
-                             consensus_n=consensus_n, consensus_weight=consensus_weight)
+                             consensus_n=consensus_n, consensus_weight=consensus_weight, context=context,
+                             context_ngram=crules[0], context_penalty=crules[1])
     return decoder
 
 
@@ -1047,9 +1232,11 @@ def _sample_choose(lp, temperature, top_k, top_p, u):
     return torch.where(dead, arg, pick), torch.where(dead, zero, logq)
 
 
-def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, temperature, top_k, top_p, seed, rules=None):
+def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, temperature, top_k, top_p, seed, rules=None,
+                  context=None):
     """rules 1-6 over full re-runs of model.inference on the (B*n)-row prefix batch -> (tokens (B, n, steps + 1),
-    sum_logp (B, n), step logp (B, n, steps), step logq (B, n, steps), steps); rules: what _rule_args returned"""
+    sum_logp (B, n), step logp (B, n, steps), step logq (B, n, steps), steps); rules: what _rule_args returned, context:
+    what _context returned"""
     import numpy as np
     B = fs['audio'].shape[0]
     dev = fs['audio'].device
@@ -1063,7 +1250,9 @@ def _sample_rerun(model, fs, max_len, start_idx, end_idx, pad_idx, modality, n, 
     steps = 0
     while steps < max_len:
         lp = _rerun_logp(model, x, rep, hist, modality, pad_idx)
-        if rules is not None:
+        if context is not None:
+            lp = _apply_context_rules(lp, hist, steps, rules, end_idx, pad_idx, context[0], n, context[1])
+        elif rules is not None:
             lp = _apply_rules(lp, hist, steps, *rules, end_idx, pad_idx)
         lp = lp.double()
         u = torch.from_numpy(uniform01(seed, rows + np.uint64(steps))).to(dev)

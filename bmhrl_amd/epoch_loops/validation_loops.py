@@ -169,7 +169,7 @@ def _video_durations(reference_paths):
     return durations
 
 
-def validation_learned_props_loop(cfg, model, proposals, decoder, epoch, TBoard, dataset, evaluator=None):
+def validation_learned_props_loop(cfg, model, proposals, decoder, epoch, TBoard, dataset, evaluator=None, paragraph=False):
     """Captions predicted proposals -- the reference's `learned_props` phase -- from the videos' full-length feature files:
     `proposals` is a submission dictionary or the path of a prop_results_*.json.  Its segments are grouped by video in the
     file's order; cfg.inference_batch_size videos at a time are loaded whole (predict.VideoFeatures: each file read once,
@@ -177,8 +177,11 @@ def validation_learned_props_loop(cfg, model, proposals, decoder, epoch, TBoard,
     predict.caption_segments.  Durations come from the ground-truth files cfg.reference_paths.  Writes
     captioning_results_learned_props_e<epoch>.json and scores it against cfg.reference_paths at cfg.tIoUs; returns as
     validation_1by1_loop: the metrics, None when cfg.log_path is None, the predictions dictionary when the evaluator is not
-    importable.  dataset: vocabulary and special tokens (train_vocab.itos, start_idx, end_idx, pad_idx)."""
+    importable.  dataset: vocabulary and special tokens (train_vocab.itos, start_idx, end_idx, pad_idx).  paragraph=True:
+    predict.caption_segments' time-ordered mode -- a video's proposals are captioned in time order, each with the video's
+    earlier captions as the decoder's context."""
     from ..predict import VideoFeatures, caption_segments
+    mode = {"paragraph": True} if paragraph else {}
     if evaluator is None:
         evaluator = getattr(cfg, "caption_evaluator", None)
     model.eval()
@@ -196,7 +199,7 @@ def validation_learned_props_loop(cfg, model, proposals, decoder, epoch, TBoard,
         features = VideoFeatures.from_npy(cfg, ids, [durations[v] for v in ids], cfg.pad_feats_up_to, dataset.pad_idx,
                                           torch.device(cfg.device))
         segments = [[tuple(seg["timestamp"]) for seg in segs] for _, segs in group]
-        for video_id, caps in zip(ids, caption_segments(cfg, model, features, segments, decoder, dataset)):
+        for video_id, caps in zip(ids, caption_segments(cfg, model, features, segments, decoder, dataset, **mode)):
             if caps:
                 predictions["results"].setdefault(video_id, []).extend(caps)
     if cfg.log_path is None:

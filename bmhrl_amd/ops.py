@@ -1102,6 +1102,39 @@ def logit_rules(logp, ld, rows, V, hist, t, ngram, min_len, penalty, end_idx, pa
             pad_idx)
 
 
+LOGIT_RULES_MAX_CTX = 1024                    # BMHRL_LOGIT_RULES_MAX_CTX of include/bmhrl_hip.h
+LOGIT_RULES_CTX_MAX_V = 65536                 # BMHRL_LOGIT_RULES_CTX_MAX_V
+
+
+def logit_rules_ctx(logp, ld, rows, V, hist, t, ngram, min_len, penalty, end_idx, pad_idx, ctx, rows_per_ctx, ctx_ngram,
+                    ctx_penalty):
+    """logit_rules and the context rules C1-C2 in one launch (see bmhrl_logit_rules_ctx in include/bmhrl_hip.h): ctx
+    (rows / rows_per_ctx, cols <= LOGIT_RULES_MAX_CTX) int64 holds per clip the tokens of the video's earlier captions, an
+    entry outside [0, V) or equal to pad_idx a gap; row r reads context row r // rows_per_ctx.  V <= LOGIT_RULES_CTX_MAX_V."""
+    if not (1 <= V <= LOGIT_RULES_CTX_MAX_V and ld >= V and rows >= 1 and logp.dtype == torch.float32
+            and logp.numel() >= (rows - 1) * ld + V):
+        raise ValueError(f"logit_rules_ctx: need 1 <= V <= {LOGIT_RULES_CTX_MAX_V} and fp32 logp rows (rows, ld >= V)")
+    if not (ngram >= 0 and min_len >= 0 and math.isfinite(penalty) and penalty > 0):
+        raise ValueError("logit_rules_ctx: need ngram >= 0, min_len >= 0 and a finite penalty > 0")
+    if not (ctx_ngram >= 0 and math.isfinite(ctx_penalty) and ctx_penalty > 0):
+        raise ValueError("logit_rules_ctx: need ctx_ngram >= 0 and a finite ctx_penalty > 0")
+    if not (0 <= end_idx < V and 0 <= pad_idx < V):
+        raise ValueError("logit_rules_ctx: need 0 <= end_idx < V and 0 <= pad_idx < V")
+    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != rows or hist.stride(1) != 1 or \
+            not 1 <= hist.shape[1] <= LOGIT_RULES_MAX_HIST or hist.stride(0) != hist.shape[1]:
+        raise ValueError(f"logit_rules_ctx: hist must be a contiguous (rows, cols <= {LOGIT_RULES_MAX_HIST}) int64 buffer")
+    if not (rows_per_ctx >= 1 and rows % rows_per_ctx == 0):
+        raise ValueError("logit_rules_ctx: rows_per_ctx must be >= 1 and divide rows")
+    if ctx.dtype != torch.int64 or ctx.dim() != 2 or ctx.shape[0] != rows // rows_per_ctx or not ctx.is_contiguous() or \
+            not 1 <= ctx.shape[1] <= LOGIT_RULES_MAX_CTX:
+        raise ValueError(f"logit_rules_ctx: ctx must be a contiguous (rows / rows_per_ctx, cols <= {LOGIT_RULES_MAX_CTX}) int64 "
+                         "buffer")
+    if t.dtype != torch.int64:
+        raise ValueError("logit_rules_ctx: t is an int64 word")
+    _launch("bmhrl_logit_rules_ctx", logp, ld, rows, V, hist, hist.stride(0), t, int(ngram), int(min_len), float(penalty),
+            end_idx, pad_idx, ctx, ctx.shape[1], int(rows_per_ctx), int(ctx_ngram), float(ctx_penalty))
+
+
 # ---- consensus choice among a clip's hypotheses (csrc/consensus.hip)
 CONSENSUS_MAX_STEPS = 256                     # BMHRL_CONSENSUS_MAX_STEPS of include/bmhrl_hip.h (K: BEAM_MAX)
 CONSENSUS_MAX_N = 4                           # BMHRL_CONSENSUS_MAX_N

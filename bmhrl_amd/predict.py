@@ -153,11 +153,51 @@ def _token_ids(cfg, vocab_or_dataset):
     return x.itos, x.stoi[cfg.start_token], x.stoi[cfg.end_token], x.stoi[cfg.pad_token]
 
 
-def caption_segments(cfg, cap_model, features: VideoFeatures, segments, decoder, vocab_or_dataset, batch_size=None):
+PARAGRAPH_MAX_CONTEXT = 1024          # ops.LOGIT_RULES_MAX_CTX: the entries of a clip's context
+
+
+def caption_tokens(row, end_idx, pad_idx):
+    """the words of a decoded row as a context sentence: the generated tokens after the start token, up to but without the
+    first end_idx, pads dropped"""
+    words = [int(v) for v in row[1:]]
+    if end_idx in words:
+        words = words[:words.index(end_idx)]
+    return [v for v in words if v != pad_idx]
+
+
+def paragraph_context(sentences, pad_idx, context_sentences=None, limit=PARAGRAPH_MAX_CONTEXT):
+    """the context of a clip from its video's earlier captions (lists of token ids, oldest first): only the last
+    context_sentences of them when that is given, one pad_idx between sentences, and whole oldest sentences dropped until
+    the result holds at most `limit` entries (a single sentence longer than that leaves an empty context)"""
+    if context_sentences is not None:
+        sentences = sentences[max(0, len(sentences) - int(context_sentences)):]
+    sentences = list(sentences)
+    while sentences and sum(len(x) for x in sentences) + len(sentences) - 1 > limit:
+        sentences = sentences[1:]
+    out = []
+    for i, sent in enumerate(sentences):
+        out += ([pad_idx] if i else []) + list(sent)
+    return out
+
+
+def caption_segments(cfg, cap_model, features: VideoFeatures, segments, decoder, vocab_or_dataset, batch_size=None,
+                     paragraph=False, context_sentences=None, fill_chunks=False):
     """captions segments[v] = [(start s, end s), ...] of every video of `features`, in the given order and in chunks of at
     most batch_size (cfg.inference_batch_size) clips, with `decoder` -- any factory result of bmhrl_amd.decode -- and returns
     per video the list of {"sentence", "timestamp": [start, end]}.  The crops' status words are read once, at the end: a
-    truncated or undefined crop raises."""
+    truncated or undefined crop raises.
+    paragraph=True decodes in time order instead: each video's segments are ordered by (start, end,
+    given index); wave w holds the w-th segment of every video that has one, videos in index order, in chunks of at most
+    batch_size; and the decoder is called with the keyword context= a (clips, C) int64 tensor that holds, per clip, its
+    video's w earlier captions (caption_tokens of each, oldest first, one pad_idx between sentences; only the last
+    context_sentences of them when that is given; whole oldest sentences dropped until at most 1024 entries are left).  What
+    the context does is the decoder's business: greedy_decoder(context_ngram=4) bans the earlier captions' 4-grams.  The
+    returned lists are in the given order either way.  fill_chunks (paragraph mode only): a chunk smaller than batch_size is
+    filled with copies of its last clip and the extra rows are thrown away, so that a decoder cached for the full batch
+    is reused; rows are independent, so no token changes.  Off by default: section 34 measured no gain."""
+    if paragraph:
+        return _caption_paragraphs(cfg, cap_model, features, segments, decoder, vocab_or_dataset, batch_size,
+                                   context_sentences, fill_chunks)
     from .epoch_loops.validation_loops import tokens_to_sentences
     if len(segments) != len(features):
         raise ValueError(f"caption_segments: {len(segments)} segment lists for {len(features)} videos")
@@ -187,17 +227,66 @@ def caption_segments(cfg, cap_model, features: VideoFeatures, segments, decoder,
     return results
 
 
+def _caption_paragraphs(cfg, cap_model, features, segments, decoder, vocab_or_dataset, batch_size, context_sentences,
+                        fill_chunks):
+    """caption_segments(paragraph=True)"""
+    from .epoch_loops.validation_loops import tokens_to_sentences
+    if len(segments) != len(features):
+        raise ValueError(f"caption_segments: {len(segments)} segment lists for {len(features)} videos")
+    batch_size = int(cfg.inference_batch_size if batch_size is None else batch_size)
+    if batch_size < 1:
+        raise ValueError("caption_segments: batch_size must be >= 1")
+    if context_sentences is not None and (isinstance(context_sentences, bool) or int(context_sentences) != context_sentences
+                                          or int(context_sentences) < 0):
+        raise ValueError(f"caption_segments: context_sentences must be None or an integer >= 0, got {context_sentences!r}")
+    itos, start_idx, end_idx, pad_idx = _token_ids(cfg, vocab_or_dataset)
+    # per video its segments in time order: (start, end, given index)
+    ordered = [sorted((float(s), float(e), i) for i, (s, e) in enumerate(segs)) for segs in segments]
+    results: List[List[dict]] = [[None] * len(segs) for segs in segments]
+    said: List[List[List[int]]] = [[] for _ in segments]          # per video the captions so far, as token ids
+    agent = _unwrap(cap_model)
+    status = []
+    with torch.no_grad():
+        for w in range(max([0] + [len(o) for o in ordered])):
+            wave = [(v, *o[w]) for v, o in enumerate(ordered) if len(o) > w]
+            for i in range(0, len(wave), batch_size):
+                chunk = wave[i:i + batch_size]
+                n = len(chunk)
+                if fill_chunks and n < batch_size:
+                    chunk = chunk + [chunk[-1]] * (batch_size - n)
+                fs, st = features.crop([c[0] for c in chunk], [c[1:3] for c in chunk], cfg.modality, return_status=True)
+                status.append(st)
+                rows = [paragraph_context(said[c[0]], pad_idx, context_sentences) for c in chunk]
+                width = max([1] + [len(r) for r in rows])
+                context = torch.tensor([r + [pad_idx] * (width - len(r)) for r in rows], dtype=torch.int64).view(len(rows), width)
+                ints = decoder(agent, fs, cfg.max_len, start_idx, end_idx, pad_idx, cfg.modality,
+                               context=context.to(features.device))
+                ints = ints[:n].cpu().numpy()
+                sentences = tokens_to_sentences(ints, itos)
+                for (v, s, e, given), row, sent in zip(chunk[:n], ints, sentences):
+                    results[v][given] = {"sentence": sent, "timestamp": [s, e]}
+                    said[v].append(caption_tokens(row, end_idx, pad_idx))
+    if status:
+        truncated, undefined = torch.stack([st.amax(0) for st in status]).sum(0).tolist()
+        if truncated or undefined:
+            raise RuntimeError(f"caption_segments: {truncated} crops were truncated and {undefined} had no defined row range "
+                               "(a duration that is not > 0 or a time that is not finite)")
+    return results
+
+
 class VideoCaptioner:
     """proposals and their captions for whole videos.  cfg: the captioning config (modality, max_len, inference_batch_size)
     with the post-processing fields of the proposal config (max_prop_per_vid, nms_tiou_thresh); prop_model: a
     MultimodalProposalGenerator; cap_model: the agent; dataset: the training data set (vocabulary and special tokens);
-    decoder: a factory result of bmhrl_amd.decode, greedy when None."""
+    decoder: a factory result of bmhrl_amd.decode, greedy when None; paragraph / context_sentences: caption_segments' -- the
+    proposals of a video are captioned in time order, each with the video's earlier captions as its context."""
 
-    def __init__(self, cfg, prop_model, cap_model, dataset, decoder=None):
+    def __init__(self, cfg, prop_model, cap_model, dataset, decoder=None, paragraph=False, context_sentences=None):
         if decoder is None:
             from .decode import greedy_decoder
             decoder = greedy_decoder()
         self.cfg, self.prop_model, self.cap_model, self.dataset, self.decoder = cfg, prop_model, cap_model, dataset, decoder
+        self.paragraph, self.context_sentences = bool(paragraph), context_sentences
 
     def proposals(self, features: VideoFeatures):
         """per video the entries {"sentence": "", "proposal_score", "timestamp"} AnetPredictions.add_new_predictions would
@@ -212,7 +301,8 @@ class VideoCaptioner:
     def caption(self, features: VideoFeatures, proposals, batch_size=None):
         """caption_segments on the proposals' (rounded) times; each entry keeps its proposal_score"""
         captions = caption_segments(self.cfg, self.cap_model, features, [[p["timestamp"] for p in props] for props in proposals],
-                                    self.decoder, self.dataset, batch_size)
+                                    self.decoder, self.dataset, batch_size, paragraph=self.paragraph,
+                                    context_sentences=self.context_sentences)
         for caps, props in zip(captions, proposals):
             for cap, prop in zip(caps, props):
                 cap["proposal_score"] = prop["proposal_score"]

@@ -830,6 +830,33 @@ int bmhrl_logit_rules(float* logp, int64_t ld, int32_t rows, int32_t V, const in
                       bmhrl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Paragraph-aware constrained decoding (bmhrl_amd/decode.py; rules C1-C5 of its constraints section): the three rules of
+ * the entry above and the context rules in one launch, which a token step issues IN PLACE of the plain one.  ctx holds
+ * rows / rows_per_ctx contexts of ld_ctx int64 entries each (row stride ld_ctx): the tokens of a clip's earlier captions.
+ * An entry is a word when 0 <= id < V and id != pad_idx, anything else a gap.  Row r reads context row r / rows_per_ctx.
+ *  1.  as above;
+ *  C1. ctx_penalty != 1: for every distinct word id v of the context, lp[v] = lp[v] * ctx_penalty (one fp32 multiply per
+ *      id, after rule 1's where an id is in both);
+ *  2.  as above;
+ *  C2. ctx_ngram = n_c >= 1 and t >= n_c - 1: for every j in [0, ld_ctx - n_c] whose window ctx[j .. j+n_c-1] is all words
+ *      and whose first n_c - 1 entries equal s[t-n_c+2 .. t] (the last n_c - 1 generated tokens, never the start token;
+ *      empty for n_c = 1), lp[ctx[j+n_c-1]] = -inf.  A window that holds a gap matches nothing;
+ *  3.  as above;
+ *  in this order.  Columns V .. ld-1 and other rows are never touched, and a t outside [0, ld_hist - 1] writes nothing.
+ *  Everything the entry above refuses is refused here, and so are a null ctx, ld_ctx outside
+ *  [1, BMHRL_LOGIT_RULES_MAX_CTX], rows_per_ctx < 1 or rows % rows_per_ctx != 0, ctx_ngram < 0, a ctx_penalty that is not
+ *  finite or <= 0, and V > BMHRL_LOGIT_RULES_CTX_MAX_V (C1's map of one bit per token id in LDS), all with -22.
+ *  Deterministic: the only atomic is an LDS or-and-return that picks which context position does an id's one multiply;
+ *  global memory sees plain stores, and equal inputs give equal bits.
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_LOGIT_RULES_MAX_CTX 1024
+#define BMHRL_LOGIT_RULES_CTX_MAX_V 65536
+int bmhrl_logit_rules_ctx(float* logp, int64_t ld, int32_t rows, int32_t V, const int64_t* hist, int64_t ld_hist,
+                          const int64_t* t, int32_t ngram, int32_t min_len, float penalty, int32_t end_idx, int32_t pad_idx,
+                          const int64_t* ctx, int64_t ld_ctx, int32_t rows_per_ctx, int32_t ctx_ngram, float ctx_penalty,
+                          bmhrl_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Consensus (minimum-Bayes-risk) utilities of a clip's hypotheses (bmhrl_amd/decode.py; rules R1-R6 are at the top of its
  * consensus section).  hist is a decoder's token history: row r = b * K + k holds hypothesis k of clip b, row stride ld,
  * column 0 the start token and columns 1 .. steps the generated tokens; columns beyond `steps` are never read.  The words
