@@ -12,6 +12,8 @@
 //                    IS "conf descending, ties to the smaller row".  Each pass sorts chunks of 4096 keys in LDS and keeps
 //                    the k largest of a chunk; passes repeat on the survivors until one chunk is left, which the last kernel
 //                    sorts, gathers, trims and suppresses (k-step greedy loop, the inner comparison across the lanes).
+//   proposal_select_soft  the same passes keeping a pool of m <= 1024 keys, then a last kernel that picks k times by the
+//                    CURRENT score and lowers the scores of overlapping rows (Soft-NMS).
 //
 // Reference: utilities/proposal_utils.py (tiou_vectorized, select_topk_predictions, get_corner_coords, trim_proposals,
 // non_max_suppresion), in fp32 and in its order of operations.  Nothing here may be contracted or reassociated:
@@ -355,6 +357,140 @@ __global__ __launch_bounds__(kSortThreads) void select_final_kernel(const float*
 
 inline long chunks_of(long m) { return (m + kChunk - 1) / kChunk; }
 
+// ------------------------------------------------------------------------------------------------ soft select
+// DESIGN.md section 35.  A pool of m <= 1024 rows per video; a pick is the arg-max of the CURRENT scores (ties to the
+// smaller rank), and the rows that overlap the pick are retired (hard) or lose score (linear, Gaussian) instead.
+constexpr int kSoftRows = BMHRL_PROPOSAL_SOFT_MAX_M / kSortThreads;      // pool rows a thread owns: tid and tid + 512
+
+// the float whose order_key is the upper half of a key
+__device__ __forceinline__ float key_score(uint64_t key) {
+  const uint32_t u = (uint32_t)(key >> 32);
+  return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+}
+
+__device__ __forceinline__ uint64_t wave_max_key(uint64_t v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
+    const uint64_t w = ((uint64_t)hi << 32) | (uint64_t)lo;
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+// grid (B): the last chunk -- sort, gather the pool, corners, trim, then at most k picks.  A thread keeps the current scores
+// of its (at most two) pool rows in registers; start / end / row of the whole pool are in LDS.  One barrier per pick: the
+// eight wave maxima go to slot[pick & 1] and every thread reduces them itself, so a slot is written again only behind the
+// barrier of the pick between, which no thread passes before it has read the slot.
+__global__ __launch_bounds__(kSortThreads) void select_soft_kernel(const float* __restrict__ pred, long n,
+                                                                   const uint64_t* __restrict__ keys_in, long mk,
+                                                                   const float* __restrict__ durations, int m, int k, int method,
+                                                                   float tiou_thresh, float sigma, float min_score,
+                                                                   float* __restrict__ props, int* __restrict__ rows,
+                                                                   int* __restrict__ count) {
+  __shared__ uint64_t keys[kChunk];
+  __shared__ float st[BMHRL_PROPOSAL_SOFT_MAX_M], en[BMHRL_PROPOSAL_SOFT_MAX_M];
+  __shared__ int rw[BMHRL_PROPOSAL_SOFT_MAX_M];
+  __shared__ uint64_t slot[2][kSortThreads / WAVE];
+  const long b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int ns = load_chunk(keys, keys_in ? nullptr : pred, keys_in, b, keys_in ? mk : n, 0);
+  sort_desc(keys, ns);
+  const float dur = durations[b];
+  float sc[kSoftRows];
+  bool alive[kSoftRows];
+#pragma unroll
+  for (int r = 0; r < kSoftRows; ++r) {
+    const int j = tid + r * kSortThreads;                   // the row's rank
+    sc[r] = 0.f;
+    alive[r] = false;
+    if (j < m) {
+      const uint64_t kv = j < ns ? keys[j] : 0;
+      float s = 0.f, e = 0.f;
+      int row = -1;
+      if (kv != 0) {
+        const long rr = (long)(0xFFFFFFFFu - (uint32_t)kv);
+        if (rr < n) {                 // (always: keys only ever hold rows of this video)
+          const float* p = pred + (b * n + rr) * 3;
+          const float centre = p[0], length = p[1];
+          sc[r] = p[2];
+          s = centre - length / 2.f;
+          e = centre + length / 2.f;
+          s = fminf(fmaxf(s, 0.f), dur);
+          e = fminf(e, dur);
+          row = (int)rr;
+          alive[r] = true;
+        }
+      }
+      st[j] = s;
+      en[j] = e;
+      rw[j] = row;
+    }
+  }
+  __syncthreads();
+  float* out = props + (b * k) * 3;
+  int* out_rows = rows ? rows + b * k : nullptr;
+  int picked = 0;
+  for (; picked < k; ++picked) {
+    uint64_t best = 0;
+#pragma unroll
+    for (int r = 0; r < kSoftRows; ++r)
+      if (alive[r]) {
+        const uint64_t key = ((uint64_t)order_key(sc[r]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(tid + r * kSortThreads));
+        best = key > best ? key : best;
+      }
+    best = wave_max_key(best);
+    uint64_t* sl = slot[picked & 1];
+    if ((tid & (WAVE - 1)) == 0) sl[tid / WAVE] = best;
+    __syncthreads();
+    best = sl[0];
+#pragma unroll
+    for (int w = 1; w < kSortThreads / WAVE; ++w) best = sl[w] > best ? sl[w] : best;
+    if (best == 0) break;             // nothing alive (the same key in every thread: a uniform exit)
+    const float score = key_score(best);
+    if (score < min_score) break;
+    const int pick = (int)(0xFFFFFFFFu - (uint32_t)best);
+    const float s1 = st[pick], e1 = en[pick];
+    if (tid == 0) {
+      out[picked * 3 + 0] = s1;
+      out[picked * 3 + 1] = e1;
+      out[picked * 3 + 2] = score;
+      if (out_rows) out_rows[picked] = rw[pick];
+    }
+#pragma unroll
+    for (int r = 0; r < kSoftRows; ++r) {
+      const int j = tid + r * kSortThreads;
+      if (!alive[r]) continue;
+      if (j == pick) {
+        alive[r] = false;
+        continue;
+      }
+      const float s2 = st[j], e2 = en[j];
+      const float inter = fmaxf(fminf(e1, e2) - fmaxf(s1, s2), 0.f);
+      float uni = (e1 - s1) + (e2 - s2) - inter;
+      uni = fminf(fmaxf(e1, e2) - fminf(s1, s2), uni);
+      const float t = inter / (uni + 1e-8f);
+      if (!(t < tiou_thresh)) {
+        if (method == BMHRL_NMS_HARD) {
+          alive[r] = false;
+        } else if (method == BMHRL_NMS_LINEAR) {
+          sc[r] = sc[r] * (1.f - t);
+        } else if (t != 0.f) {        // (t == 0, a disjoint row: exp(-0) is exactly 1 and the product the score's own bits)
+          const float w32 = (float)exp(-((double)t * (double)t) / (double)sigma);
+          sc[r] = sc[r] * w32;
+        }
+      }
+    }
+  }
+  for (int j = picked + tid; j < k; j += kSortThreads) {    // behind the picks
+    out[j * 3 + 0] = 0.f;
+    out[j * 3 + 1] = 0.f;
+    out[j * 3 + 2] = 0.f;
+    if (out_rows) out_rows[j] = -1;
+  }
+  if (tid == 0) count[b] = picked;
+}
+
 }  // namespace
 
 extern "C" int bmhrl_proposal_assign(const float* targets, int32_t n_targets, const float* anchors, int32_t A, float cell_sec,
@@ -424,5 +560,39 @@ extern "C" int bmhrl_proposal_select(const float* pred, int32_t B, int64_t N, co
   }
   hipLaunchKernelGGL(select_final_kernel, dim3((unsigned)B), dim3(kSortThreads), 0, S_(stream), pred, (long)N, keys_in, m, durations,
                      k, nms_tiou, props, count);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int bmhrl_proposal_select_soft(const float* pred, int32_t B, int64_t N, const float* durations, int32_t m, int32_t k,
+                                          int32_t method, float tiou_thresh, float sigma, float min_score, float* props,
+                                          int32_t* rows, int32_t* count, uint64_t* workspace, int64_t workspace_elems,
+                                          bmhrl_stream_t stream) {
+  BMHRL_CHECK_ARG(pred && durations && props && count && B >= 1 && B <= 65535);
+  BMHRL_CHECK_ARG(N >= 1 && N <= BMHRL_PROPOSAL_MAX_N && m >= 1 && m <= BMHRL_PROPOSAL_SOFT_MAX_M && k >= 1 && k <= m);
+  BMHRL_CHECK_ARG(method == BMHRL_NMS_HARD || method == BMHRL_NMS_LINEAR || method == BMHRL_NMS_GAUSSIAN);
+  BMHRL_CHECK_ARG(tiou_thresh == tiou_thresh && min_score == min_score && (method != BMHRL_NMS_GAUSSIAN || sigma > 0.f));
+  // stage one is bmhrl_proposal_select's, keeping m keys per chunk: chunks_of(c) * m candidates per pass until one chunk is left
+  long need0 = 0, need1 = 0;
+  {
+    long c = N;
+    for (int pass = 0; c > kChunk; ++pass) {
+      const long out = chunks_of(c) * m;
+      if (pass & 1) need1 = need1 > out ? need1 : out; else need0 = need0 > out ? need0 : out;
+      c = out;
+    }
+  }
+  BMHRL_CHECK_ARG(need0 == 0 || (workspace && workspace_elems >= (int64_t)B * (need0 + need1)));
+  uint64_t* buf[2] = {workspace, workspace ? workspace + (long)B * need0 : nullptr};
+  const uint64_t* keys_in = nullptr;
+  long c = N;
+  for (int pass = 0; c > kChunk; ++pass) {
+    const long nc = chunks_of(c);
+    hipLaunchKernelGGL(select_pass_kernel, dim3((unsigned)nc, (unsigned)B), dim3(kSortThreads), 0, S_(stream), pred, keys_in, c, m,
+                       buf[pass & 1]);
+    keys_in = buf[pass & 1];
+    c = nc * m;
+  }
+  hipLaunchKernelGGL(select_soft_kernel, dim3((unsigned)B), dim3(kSortThreads), 0, S_(stream), pred, (long)N, keys_in, c, durations,
+                     m, k, method, tiou_thresh, sigma, min_score, props, rows, count);
   return hip_status(hipGetLastError());
 }

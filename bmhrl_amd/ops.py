@@ -1357,6 +1357,37 @@ def proposal_select(predictions, durations, k, nms_tiou=None):
     return props, count
 
 
+PROPOSAL_SOFT_MAX_M = 1024                    # BMHRL_PROPOSAL_SOFT_MAX_M
+NMS_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}            # BMHRL_NMS_*
+
+
+def proposal_select_soft(predictions, durations, m, k, method, tiou_thresh=0.0, sigma=0.5, min_score=None):
+    """Soft-NMS over a pool (see bmhrl_proposal_select_soft): predictions (B, N, 3) fp32 rows [centre s, length s,
+    confidence], durations (B) fp32; the pool is the m rows of highest confidence, of which at most k are picked by their
+    current score.  method: "hard", "linear" or "gaussian" (or the BMHRL_NMS_* number); min_score None = no floor.  Returns
+    props (B, k, 3) = [start, end, rescored confidence] in pick order with zeros behind, rows (B, k) int32 = the picked
+    rows of `predictions` with -1 behind, and count (B) int32."""
+    if predictions.dim() != 3 or predictions.shape[2] != 3:
+        raise ValueError("proposal_select_soft: predictions (B, N, 3) expected")
+    if isinstance(method, str):
+        if method not in NMS_METHODS:
+            raise ValueError(f"proposal_select_soft: method is one of {sorted(NMS_METHODS)}, got {method!r}")
+        method = NMS_METHODS[method]
+    B, N = predictions.shape[0], predictions.shape[1]
+    _f32c(predictions, (B, N, 3), "proposal_select_soft (predictions)")
+    _f32c(durations, (B,), "proposal_select_soft (durations)")
+    m, k = int(m), int(k)
+    dev = predictions.device
+    props = torch.empty(B, max(k, 0), 3, device=dev)
+    rows = torch.empty(B, max(k, 0), dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    words = B * proposal_select_workspace(N, m) if 1 <= m <= PROPOSAL_SOFT_MAX_M else 0
+    ws = torch.empty(words, dtype=torch.int64, device=dev) if words else None
+    _launch("bmhrl_proposal_select_soft", predictions, B, N, durations, m, k, int(method), float(tiou_thresh), float(sigma),
+            float("-inf") if min_score is None else float(min_score), props, rows, count, ws, words)
+    return props, rows, count
+
+
 # ---- segment crop: the rows of temporal segments out of device-resident full-length stacks (csrc/segment_crop.hip)
 def crop_segments(src, src_len, durations, seg_video, seg_times, pad_value, T_out, out=None):
     """crop and pad P segments out of the full-length stacks of V videos (see bmhrl_crop_segments): src (V, S_pad, D) fp32,

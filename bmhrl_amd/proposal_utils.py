@@ -7,6 +7,10 @@ chain for a batch: for device input in ONE call of ops.proposal_select (csrc/pro
 host read before the single `.tolist()`), for host input through the piecewise functions.  Where the reference's `argsort`
 leaves the order of equal confidences open, both routes here put the smaller row first.
 
+Beyond the reference: Soft-NMS (`soft_nms`, cfg.nms_method "linear" / "gaussian") and a candidate pool larger than
+max_prop_per_vid (cfg.nms_candidates); `soft_nms_settings` reads the optional cfg fields, `soft_select_rows` is the route
+(ops.proposal_select_soft for device input), and a cfg without them takes the calls above unchanged.
+
 `anchors_from_segments` stands where the reference's `calc_anchors_using_kmeans` stands.  That one runs scikit-learn's KMeans
 with a random initialisation (random_state=13); scikit-learn's generator is not reproduced here.  This is a deterministic
 1-D k-means (Lloyd's iterations from quantile initial centres), so its anchors are close to, not equal to, the reference's.
@@ -16,8 +20,10 @@ from __future__ import annotations
 import contextlib
 import io
 import json
+import math
 import os
 from time import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -96,6 +102,57 @@ def non_max_suppresion(video_preds, tIoU_threshold):
     return torch.cat(kept) if kept else video_preds
 
 
+NMS_METHODS = ("hard", "linear", "gaussian")
+
+
+def soft_nms(video_preds, method, tiou_thresh=0.0, sigma=0.5, min_score=1e-3, k=None):
+    """Soft-NMS (Bodla et al. 2017) of one video's (n, F >= 3) rows (start, end, conf, ...) sorted by confidence, the
+    definition of bmhrl_proposal_select_soft in plain torch fp32 (and math.exp), bit for bit: at most k times (None: n) the
+    alive row of largest current score is picked, ties to the earlier row; a score below min_score (None: no floor) ends
+    the loop; every other alive row whose tIoU with the pick is not below tiou_thresh is removed ("hard") or rescored by
+    1 - tIoU ("linear") or exp(-tIoU^2 / sigma) ("gaussian").  Returns the picked rows in pick order, column 2 rewritten."""
+    if method not in NMS_METHODS:
+        raise ValueError(f"soft_nms: method is one of {NMS_METHODS}, got {method!r}")
+    n = len(video_preds)
+    f32 = dict(dtype=torch.float32, device=video_preds.device)
+    segs = video_preds[:, :2].to(torch.float32)
+    scores = video_preds[:, 2].to(torch.float32).clone()
+    thr = torch.tensor(tiou_thresh, **f32)
+    floor = None if min_score is None else torch.tensor(min_score, **f32)
+    sigma = torch.tensor(sigma, dtype=torch.float32).item()           # the fp32 value the kernel is handed, as a double
+    alive = torch.ones(n, dtype=torch.bool, device=video_preds.device)
+    picked, picked_scores = [], []
+    for _ in range(n if k is None else min(int(k), n)):
+        # the order-preserving integer image of the scores (-0.0 below +0.0, as the kernel's key has it); -1 = not alive
+        u = scores.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        image = torch.where(u >= 0x80000000, 0xFFFFFFFF - u, u + 0x80000000)
+        image = torch.where(alive, image, torch.full_like(image, -1))
+        best = image.max()
+        if int(best) < 0:
+            break
+        i = int(torch.nonzero(image == best)[0])                      # ties: the smaller rank
+        if floor is not None and bool(scores[i] < floor):
+            break
+        picked.append(i)
+        picked_scores.append(scores[i].clone())
+        alive[i] = False
+        tious = tiou_vectorized(segs[i:i + 1], segs, center_length=False).reshape(-1)
+        hit = alive & ~(tious < thr)
+        if method == "hard":
+            alive &= ~hit
+        elif method == "linear":
+            scores = torch.where(hit, scores * (1 - tious), scores)
+        else:
+            # float64 weights, each rounded once to fp32 (torch.tensor does that); the product is fp32
+            weights = [math.exp(-(t * t) / sigma) for t in tious[hit].tolist()]
+            scores[hit] = scores[hit] * torch.tensor(weights, **f32)
+    if not picked:
+        return video_preds[:0]
+    out = video_preds[torch.tensor(picked, device=video_preds.device)].clone()
+    out[:, 2] = torch.stack(picked_scores).to(out.dtype)
+    return out
+
+
 def postprocess_preds(model_output, cfg, batch):
     """top-cfg.max_prop_per_vid rows, corner coordinates in seconds, trimmed to the videos' durations: (B, k, F)"""
     model_output = select_topk_predictions(model_output, k=cfg.max_prop_per_vid)
@@ -115,10 +172,55 @@ def device_proposal_rows(model_output, duration_in_secs, k, nms_tiou):
     return [[row[3 * j:3 * j + 3] for j in range(int(row[-1]))] for row in packed], min(k, model_output.shape[1])
 
 
+def soft_nms_settings(cfg):
+    """(k, m, method, tiou_thresh, sigma, min_score) when cfg asks for a soft method (nms_method "linear" / "gaussian") or
+    for a pool larger than max_prop_per_vid (nms_candidates), None for every other cfg.  The fields beyond
+    max_prop_per_vid and nms_tiou_thresh are optional: nms_method None / "hard", nms_candidates = max_prop_per_vid,
+    soft_nms_sigma 0.5, soft_nms_min_score 1e-3 (no floor with "hard").  nms_tiou_thresh None: 0.0 for the soft methods
+    (every overlapping row is rescored), no suppression for "hard"."""
+    method = getattr(cfg, "nms_method", None) or "hard"
+    if method not in NMS_METHODS:
+        raise ValueError(f"nms_method is None or one of {NMS_METHODS}, got {method!r}")
+    k = int(cfg.max_prop_per_vid)
+    m = getattr(cfg, "nms_candidates", None)
+    m = k if m is None else int(m)
+    if method == "hard" and m <= k:
+        return None
+    if m < k:
+        raise ValueError(f"nms_candidates ({m}) is the pool max_prop_per_vid ({k}) proposals are picked from: it cannot be smaller")
+    thr = cfg.nms_tiou_thresh
+    if method == "hard":
+        return k, m, method, float("inf") if thr is None else thr, 0.5, None
+    return k, m, method, 0.0 if thr is None else thr, getattr(cfg, "soft_nms_sigma", 0.5), getattr(cfg, "soft_nms_min_score", 1e-3)
+
+
+def soft_select_rows(model_output, duration_in_secs, k, m, method, tiou_thresh, sigma, min_score):
+    """select_rows for the settings of soft_nms_settings: the m rows of highest confidence are the pool, at most k are
+    picked.  Device input within the kernel's limits in one call of ops.proposal_select_soft and one device-to-host copy,
+    anything else through postprocess_preds (with k := m) and soft_nms; both give the same bits."""
+    from . import ops
+    B, N = model_output.shape[0], model_output.shape[1]
+    m = min(int(m), N)
+    k_eff = min(int(k), m)
+    if model_output.is_cuda and 1 <= k_eff and m <= ops.PROPOSAL_SOFT_MAX_M and N <= ops.PROPOSAL_MAX_N and \
+            model_output.shape[2] == 3:
+        dur = torch.as_tensor(duration_in_secs, dtype=torch.float32).to(model_output.device, non_blocking=True)
+        props, _, count = ops.proposal_select_soft(model_output.detach().float().contiguous(), dur, m, k_eff, method, tiou_thresh,
+                                                   sigma, min_score)
+        packed = torch.cat([props.view(B, -1), count.view(B, 1).to(props.dtype)], dim=1).tolist()
+        return [[row[3 * j:3 * j + 3] for j in range(int(row[-1]))] for row in packed], min(int(k), N)
+    pool = postprocess_preds(model_output, SimpleNamespace(max_prop_per_vid=m), {"duration_in_secs": duration_in_secs})
+    return [soft_nms(video_preds, method, tiou_thresh, sigma, min_score, k_eff).tolist() for video_preds in pool], min(int(k), N)
+
+
 def select_rows(model_output, cfg, batch):
     """(per video the (start, end, conf) rows that survive top-k, trimming and NMS, as Python lists; rows considered per
-    video): device input in one call of ops.proposal_select, anything else through the piecewise functions"""
+    video): device input in one call of ops.proposal_select, anything else through the piecewise functions.  A cfg with a
+    soft nms_method or with nms_candidates > max_prop_per_vid goes through soft_select_rows instead."""
     from . import ops
+    soft = soft_nms_settings(cfg)
+    if soft is not None:
+        return soft_select_rows(model_output, batch["duration_in_secs"], *soft)
     on_device = model_output.is_cuda and 1 <= int(cfg.max_prop_per_vid) <= ops.PROPOSAL_MAX_K and \
         1 <= model_output.shape[1] <= ops.PROPOSAL_MAX_N and model_output.shape[2] == 3
     if on_device:

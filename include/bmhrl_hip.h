@@ -959,6 +959,30 @@ int bmhrl_proposal_head(const float* x, const float* anchors, float cell_sec, in
                         float* partials, uint32_t* counter, bmhrl_stream_t stream);
 int bmhrl_proposal_select(const float* pred, int32_t B, int64_t N, const float* durations, int32_t k, float nms_tiou,
                           float* props, int32_t* count, uint64_t* workspace, int64_t workspace_elems, bmhrl_stream_t stream);
+/* bmhrl_proposal_select_soft: Soft-NMS over a pool.  pred, durations as for bmhrl_proposal_select.
+ *  Per video the pool is the min(m, N) rows of highest confidence in that call's order (ties to the smaller row); rank = a
+ *  row's position in it; corners and trimming as above.  Then at most k picks: the alive row of largest CURRENT score is
+ *  picked, ties to the smaller rank (the 64-bit key (image(score) << 32) | (0xFFFFFFFF - rank)); a score < min_score ends
+ *  the loop (min_score = -INFINITY: no floor); otherwise (start, end, current score, row) is emitted and the row retired,
+ *  and every other alive row q with t = tIoU(picked, q) not < tiou_thresh (the fp32 tIoU above) is
+ *   BMHRL_NMS_HARD      retired
+ *   BMHRL_NMS_LINEAR    rescored: score_q = score_q * (1.f - t), fp32
+ *   BMHRL_NMS_GAUSSIAN  rescored: score_q = score_q * (float)exp(-((double)t * (double)t) / (double)sigma), the product fp32.
+ *  props (B, k, 3) = [start, end, rescored confidence] in pick order, zeros behind; rows (B, k) int32 = the picked rows'
+ *  indices in pred, -1 behind (may be null); count (B) int32.  For non-negative confidences the emitted scores never
+ *  increase.  Confidences are expected finite.  BMHRL_NMS_HARD with m == k <= BMHRL_PROPOSAL_MAX_K gives
+ *  bmhrl_proposal_select's bits.  A fixed number of launches, nothing read back.  -22: a null pred / durations / props /
+ *  count; B outside [1, 65535]; N outside [1, BMHRL_PROPOSAL_MAX_N]; m outside [1, BMHRL_PROPOSAL_SOFT_MAX_M]; k outside
+ *  [1, m]; an unknown method; a NaN tiou_thresh or min_score; sigma not > 0 with BMHRL_NMS_GAUSSIAN; a workspace smaller
+ *  than bmhrl_proposal_select's rule gives with k := m. */
+#define BMHRL_PROPOSAL_SOFT_MAX_M 1024
+#define BMHRL_NMS_HARD 0
+#define BMHRL_NMS_LINEAR 1
+#define BMHRL_NMS_GAUSSIAN 2
+int bmhrl_proposal_select_soft(const float* pred, int32_t B, int64_t N, const float* durations, int32_t m, int32_t k,
+                               int32_t method, float tiou_thresh, float sigma, float min_score, float* props,
+                               int32_t* rows, int32_t* count, uint64_t* workspace, int64_t workspace_elems,
+                               bmhrl_stream_t stream);
 
 /* ---- segment crop (csrc/segment_crop.hip) --------------------------------------------------------
  * Cuts and pads the rows of P temporal segments out of full-length feature stacks that are resident on the device: the
