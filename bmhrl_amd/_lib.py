@@ -157,6 +157,7 @@ PROTOTYPES = {
                             ptr],
     "bmhrl_proposal_select": [ptr, i32, i64, ptr, i32, f32, ptr, ptr, ptr, i64, ptr],
     "bmhrl_proposal_select_soft": [ptr, i32, i64, ptr, i32, i32, i32, f32, f32, f32, ptr, ptr, ptr, ptr, i64, ptr],
+    "bmhrl_proposal_chain": [ptr, ptr, i32, i32, i32, f32, f32, f32, f32, ptr, ptr, ptr, ptr, ptr],
     "bmhrl_tiou_hits": [ptr, i32, ptr, i32, ptr, ptr, ptr, i32, ptr, i32, i32, ptr, i64, ptr, i64, ptr],
     "bmhrl_tiou_pairs": [ptr, i32, ptr, i32, ptr, ptr, ptr, i32, f64, ptr, i64, ptr, i64, ptr],
     "bmhrl_crop_segments": [ptr, ptr, ptr, i32, i32, i32, ptr, ptr, i32, f32, i32, ptr, ptr, ptr, ptr, ptr],

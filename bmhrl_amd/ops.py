@@ -1388,6 +1388,34 @@ def proposal_select_soft(predictions, durations, m, k, method, tiou_thresh=0.0, 
     return props, rows, count
 
 
+PROPOSAL_CHAIN_MAX_P = 1024                   # BMHRL_PROPOSAL_CHAIN_MAX_P
+PROPOSAL_CHAIN_MAX_L = 32                     # BMHRL_PROPOSAL_CHAIN_MAX_L
+
+
+def proposal_chain(props, count, max_events, max_tiou=0.0, overlap_weight=0.0, event_cost=0.0, min_length=0.2):
+    """event-chain selection (see bmhrl_proposal_chain, csrc/event_chain.hip): props (B, P, 3) fp32 rows [start, end, score]
+    and count (B) int32 as proposal_select / proposal_select_soft return them (count None = all P rows).  Per video the
+    time-ordered chain of at most max_events eligible rows that maximises the sum of (score - event_cost) minus
+    overlap_weight times the tIoU of neighbours, neighbours overlapping by at most max_tiou.  Returns events (B, max_events,
+    3) = the chosen rows in time order with zeros behind, chain (B, max_events) int32 = their row indices with -1 behind,
+    length (B) int32 and value (B) fp32.  One launch, nothing read back."""
+    if props.dim() != 3 or props.shape[2] != 3:
+        raise ValueError("proposal_chain: props (B, P, 3) expected")
+    B, P = props.shape[0], props.shape[1]
+    _f32c(props, (B, P, 3), "proposal_chain (props)")
+    if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B,) or not count.is_contiguous()):
+        raise ValueError(f"proposal_chain (count): expected a contiguous int32 tensor of shape {(B,)}")
+    L = int(max_events)
+    dev = props.device
+    events = torch.empty(B, max(L, 0), 3, device=dev)
+    chain = torch.empty(B, max(L, 0), dtype=torch.int32, device=dev)
+    length = torch.empty(B, dtype=torch.int32, device=dev)
+    value = torch.empty(B, device=dev)
+    _launch("bmhrl_proposal_chain", props, count, B, P, L, float(max_tiou), float(overlap_weight), float(event_cost),
+            float(min_length), events, chain, length, value)
+    return events, chain, length, value
+
+
 # ---- segment crop: the rows of temporal segments out of device-resident full-length stacks (csrc/segment_crop.hip)
 def crop_segments(src, src_len, durations, seg_video, seg_times, pad_value, T_out, out=None):
     """crop and pad P segments out of the full-length stacks of V videos (see bmhrl_crop_segments): src (V, S_pad, D) fp32,

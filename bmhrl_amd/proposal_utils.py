@@ -9,7 +9,10 @@ leaves the order of equal confidences open, both routes here put the smaller row
 
 Beyond the reference: Soft-NMS (`soft_nms`, cfg.nms_method "linear" / "gaussian") and a candidate pool larger than
 max_prop_per_vid (cfg.nms_candidates); `soft_nms_settings` reads the optional cfg fields, `soft_select_rows` is the route
-(ops.proposal_select_soft for device input), and a cfg without them takes the calls above unchanged.
+(ops.proposal_select_soft for device input), and a cfg without them takes the calls above unchanged.  Event-chain
+selection (`event_chain`, cfg.chain_max_events and the other fields of `chain_settings`): of the rows any of those routes
+selects, the time-ordered chain of at most L low-overlap events of largest total confidence, found exactly (on the device
+by ops.proposal_chain, fed by the select kernels' output); `chain_predictions` applies it to a submission dictionary.
 
 `anchors_from_segments` stands where the reference's `calc_anchors_using_kmeans` stands.  That one runs scikit-learn's KMeans
 with a random initialisation (random_state=13); scikit-learn's generator is not reproduced here.  This is a deterministic
@@ -153,6 +156,81 @@ def soft_nms(video_preds, method, tiou_thresh=0.0, sigma=0.5, min_score=1e-3, k=
     return out
 
 
+CHAIN_MAX_EVENTS = 32                   # BMHRL_PROPOSAL_CHAIN_MAX_L of include/bmhrl_hip.h
+
+
+def event_chain(video_rows, max_events, max_tiou=0.0, overlap_weight=0.0, event_cost=0.0, min_length=0.2):
+    """Event-chain selection of one video's (n, F >= 3) rows (start, end, score, ...), the definition of
+    bmhrl_proposal_chain in plain torch fp32, bit for bit: among the rows longer than min_length whose score exceeds
+    event_cost, the chain of at most max_events rows with starts and ends both non-decreasing and a tIoU of neighbours of at
+    most max_tiou that maximises the sum of (score - event_cost) minus overlap_weight times the neighbours' tIoUs (by
+    dynamic programming over the levels; the first maximum wins everywhere).  Returns (the chosen rows in time order, their
+    indices in video_rows as a list, the chain's value as a float; 0.0 for an empty chain)."""
+    L = int(max_events)
+    if not 1 <= L <= CHAIN_MAX_EVENTS:
+        raise ValueError(f"event_chain: max_events is 1 .. {CHAIN_MAX_EVENTS}, got {max_events}")
+    dev = video_rows.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    tau, lam, cost, shortest = (torch.tensor(float(x), **f32) for x in (max_tiou, overlap_weight, event_cost, min_length))
+    if not all(bool(x >= 0) for x in (tau, lam, cost, shortest)):
+        raise ValueError("event_chain: max_tiou, overlap_weight, event_cost and min_length are numbers >= 0")
+    start, end, score = (video_rows[:, c].to(torch.float32) for c in range(3))
+    gain = score - cost
+    idx = torch.nonzero(((end - start) > shortest) & (score == score) & (gain > 0)).reshape(-1)
+    n = len(idx)
+    if n == 0:
+        return video_rows[:0], [], 0.0
+    # (start, end, index) order: two stable sorts, the primary key last (+ 0.0: -0.0 and 0.0 are one value)
+    idx = idx[torch.argsort(end[idx] + 0.0, stable=True)]
+    idx = idx[torch.argsort(start[idx] + 0.0, stable=True)]
+    s, e, g = start[idx], end[idx], gain[idx]
+    t = tiou_vectorized(torch.stack([s, e], dim=1), torch.stack([s, e], dim=1), center_length=False)       # t[i, j]
+    place = torch.arange(n, device=dev)
+    allowed = (place.view(n, 1) < place.view(1, n)) & (e.view(n, 1) <= e.view(1, n)) & (t <= tau)
+    penalty = lam * t
+    neg = torch.tensor(float("-inf"), **f32)
+    V, parents = [g], [None]
+    for _ in range(2, L + 1):
+        cand = (V[-1].view(n, 1) - penalty) + g.view(1, n)
+        cand = torch.where(allowed & (V[-1] > neg).view(n, 1) & (cand > neg), cand, neg)              # (NaN > -inf is False)
+        top = cand.max(dim=0).values
+        if not bool((top > neg).any()):
+            break
+        parents.append(torch.where(cand == top.view(1, n), place.view(n, 1), n).min(dim=0).values)    # the first maximum
+        V.append(top)
+    V = torch.stack(V)
+    best = V.max()
+    l, j = (int(x) for x in torch.nonzero(V == best)[0])    # row-major: the smaller level, then the earlier position
+    picked = []
+    while True:
+        picked.append(int(idx[j]))
+        if l == 0:
+            break
+        j, l = int(parents[l][j]), l - 1
+    picked.reverse()
+    return video_rows[torch.tensor(picked, device=dev)], picked, float(best)
+
+
+def chain_settings(cfg):
+    """(max_events, max_tiou, overlap_weight, event_cost, min_length) when cfg sets chain_max_events, None for every other
+    cfg.  The other fields are optional: chain_max_tiou 0.0, chain_overlap_weight 0.0, chain_event_cost 0.0,
+    chain_min_length 0.2 (rows_to_segments' `shortest`).  Raises ValueError on what bmhrl_proposal_chain would refuse."""
+    L = getattr(cfg, "chain_max_events", None)
+    if L is None:
+        return None
+    if isinstance(L, bool) or int(L) != L or not 1 <= int(L) <= CHAIN_MAX_EVENTS:
+        raise ValueError(f"chain_max_events is None or an integer 1 .. {CHAIN_MAX_EVENTS}, got {L!r}")
+    values = []
+    for field, default in (("chain_max_tiou", 0.0), ("chain_overlap_weight", 0.0), ("chain_event_cost", 0.0),
+                           ("chain_min_length", 0.2)):
+        x = getattr(cfg, field, None)
+        x = default if x is None else float(x)
+        if not x >= 0.0:                # (NaN included)
+            raise ValueError(f"{field} is a number >= 0, got {x!r}")
+        values.append(x)
+    return (int(L), *values)
+
+
 def postprocess_preds(model_output, cfg, batch):
     """top-cfg.max_prop_per_vid rows, corner coordinates in seconds, trimmed to the videos' durations: (B, k, F)"""
     model_output = select_topk_predictions(model_output, k=cfg.max_prop_per_vid)
@@ -160,14 +238,25 @@ def postprocess_preds(model_output, cfg, batch):
     return trim_proposals(model_output, batch["duration_in_secs"])
 
 
-def device_proposal_rows(model_output, duration_in_secs, k, nms_tiou):
+def _chained(props, count, chain):
+    """chain None: (props, count) as they are; the settings of chain_settings: ops.proposal_chain's (events, length) of
+    them, on the device"""
+    if chain is None:
+        return props, count
+    from . import ops
+    events, _, length, _ = ops.proposal_chain(props, count, *chain)
+    return events, length
+
+
+def device_proposal_rows(model_output, duration_in_secs, k, nms_tiou, chain=None):
     """ops.proposal_select on a device (B, N, 3) output -> (per video the surviving (start, end, conf) rows as Python lists,
-    rows considered per video), after ONE device-to-host copy"""
+    rows considered per video), after ONE device-to-host copy.  chain: the settings of chain_settings; the survivors then
+    go through ops.proposal_chain on the device and the rows are the chain, in time order."""
     from . import ops
     B = model_output.shape[0]
     dur = torch.as_tensor(duration_in_secs, dtype=torch.float32).to(model_output.device, non_blocking=True)
     k = int(k)
-    props, count = ops.proposal_select(model_output.detach().float().contiguous(), dur, k, nms_tiou)
+    props, count = _chained(*ops.proposal_select(model_output.detach().float().contiguous(), dur, k, nms_tiou), chain)
     packed = torch.cat([props.view(B, -1), count.view(B, 1).to(props.dtype)], dim=1).tolist()
     return [[row[3 * j:3 * j + 3] for j in range(int(row[-1]))] for row in packed], min(k, model_output.shape[1])
 
@@ -194,10 +283,12 @@ def soft_nms_settings(cfg):
     return k, m, method, 0.0 if thr is None else thr, getattr(cfg, "soft_nms_sigma", 0.5), getattr(cfg, "soft_nms_min_score", 1e-3)
 
 
-def soft_select_rows(model_output, duration_in_secs, k, m, method, tiou_thresh, sigma, min_score):
+def soft_select_rows(model_output, duration_in_secs, k, m, method, tiou_thresh, sigma, min_score, chain=None):
     """select_rows for the settings of soft_nms_settings: the m rows of highest confidence are the pool, at most k are
     picked.  Device input within the kernel's limits in one call of ops.proposal_select_soft and one device-to-host copy,
-    anything else through postprocess_preds (with k := m) and soft_nms; both give the same bits."""
+    anything else through postprocess_preds (with k := m) and soft_nms; both give the same bits.  chain: the settings of
+    chain_settings; the picks then go through ops.proposal_chain (on the device) or event_chain and the rows are the
+    chain, in time order."""
     from . import ops
     B, N = model_output.shape[0], model_output.shape[1]
     m = min(int(m), N)
@@ -207,31 +298,79 @@ def soft_select_rows(model_output, duration_in_secs, k, m, method, tiou_thresh, 
         dur = torch.as_tensor(duration_in_secs, dtype=torch.float32).to(model_output.device, non_blocking=True)
         props, _, count = ops.proposal_select_soft(model_output.detach().float().contiguous(), dur, m, k_eff, method, tiou_thresh,
                                                    sigma, min_score)
+        props, count = _chained(props, count, chain)
         packed = torch.cat([props.view(B, -1), count.view(B, 1).to(props.dtype)], dim=1).tolist()
         return [[row[3 * j:3 * j + 3] for j in range(int(row[-1]))] for row in packed], min(int(k), N)
     pool = postprocess_preds(model_output, SimpleNamespace(max_prop_per_vid=m), {"duration_in_secs": duration_in_secs})
-    return [soft_nms(video_preds, method, tiou_thresh, sigma, min_score, k_eff).tolist() for video_preds in pool], min(int(k), N)
+    picks = [soft_nms(video_preds, method, tiou_thresh, sigma, min_score, k_eff) for video_preds in pool]
+    if chain is not None:
+        picks = [event_chain(video_preds, *chain)[0] for video_preds in picks]
+    return [video_preds.tolist() for video_preds in picks], min(int(k), N)
 
 
 def select_rows(model_output, cfg, batch):
     """(per video the (start, end, conf) rows that survive top-k, trimming and NMS, as Python lists; rows considered per
     video): device input in one call of ops.proposal_select, anything else through the piecewise functions.  A cfg with a
-    soft nms_method or with nms_candidates > max_prop_per_vid goes through soft_select_rows instead."""
+    soft nms_method or with nms_candidates > max_prop_per_vid goes through soft_select_rows instead.  A cfg with
+    chain_max_events (chain_settings) gets, of those rows, the event chain in time order: on the device routes through
+    ops.proposal_chain before the one copy to the host, on the host route through event_chain."""
     from . import ops
     soft = soft_nms_settings(cfg)
+    chain = chain_settings(cfg)
+    extra = {} if chain is None else {"chain": chain}       # (a cfg without the chain fields makes the calls it made)
     if soft is not None:
-        return soft_select_rows(model_output, batch["duration_in_secs"], *soft)
+        return soft_select_rows(model_output, batch["duration_in_secs"], *soft, **extra)
     on_device = model_output.is_cuda and 1 <= int(cfg.max_prop_per_vid) <= ops.PROPOSAL_MAX_K and \
         1 <= model_output.shape[1] <= ops.PROPOSAL_MAX_N and model_output.shape[2] == 3
     if on_device:
-        return device_proposal_rows(model_output, batch["duration_in_secs"], cfg.max_prop_per_vid, cfg.nms_tiou_thresh)
+        return device_proposal_rows(model_output, batch["duration_in_secs"], cfg.max_prop_per_vid, cfg.nms_tiou_thresh, **extra)
     model_output = postprocess_preds(model_output, cfg, batch)
     rows = []
     for video_preds in model_output:
         if cfg.nms_tiou_thresh is not None:
             video_preds = non_max_suppresion(video_preds, cfg.nms_tiou_thresh)
+        if chain is not None:
+            video_preds = event_chain(video_preds, *chain)[0]
         rows.append(video_preds.tolist())
     return rows, model_output.shape[1]
+
+
+def chain_predictions(submission, cfg_or_settings, device=None):
+    """The event chain of every video of an ActivityNet-captions submission dictionary (a prop_results_*.json): a new
+    dictionary whose entries are the input's entries (sentence, proposal_score and timestamp untouched), filtered to the
+    chain and in time order; a video whose chain is empty is left out, as AnetPredictions leaves out a video without
+    proposals.  cfg_or_settings: a cfg with chain_max_events or the tuple of chain_settings.  With a device and at most
+    ops.PROPOSAL_CHAIN_MAX_P entries per video all videos go through ONE ops.proposal_chain call (a padded (B, P, 3)
+    table and its counts) and one copy back; otherwise through event_chain per video.  Times and scores are taken as fp32."""
+    chain = tuple(cfg_or_settings) if isinstance(cfg_or_settings, (tuple, list)) else chain_settings(cfg_or_settings)
+    if chain is None:
+        raise ValueError("chain_predictions: the cfg sets no chain_max_events")
+    results = submission["results"]
+    vids = list(results)
+
+    def score_of(entry):
+        score = entry["proposal_score"]
+        return float(score[0] if isinstance(score, (tuple, list)) else score)
+
+    tables = [[[float(p["timestamp"][0]), float(p["timestamp"][1]), score_of(p)] for p in results[v]] for v in vids]
+    P = max((len(t) for t in tables), default=0)
+    picked = [[] for _ in vids]
+    if P > 0:
+        from . import ops
+        if device is not None and torch.device(device).type == "cuda" and P <= ops.PROPOSAL_CHAIN_MAX_P:
+            padded = torch.zeros(len(vids), P, 3)
+            for b, t in enumerate(tables):
+                if t:
+                    padded[b, :len(t)] = torch.tensor(t, dtype=torch.float32)
+            count = torch.tensor([len(t) for t in tables], dtype=torch.int32)
+            _, index, length, _ = ops.proposal_chain(padded.to(device), count.to(device), *chain)
+            packed = torch.cat([index, length.view(-1, 1)], dim=1).tolist()
+            picked = [row[:row[-1]] for row in packed]
+        else:
+            picked = [event_chain(torch.tensor(t, dtype=torch.float32), *chain)[1] if t else [] for t in tables]
+    out = {key: value for key, value in submission.items() if key != "results"}
+    out["results"] = {v: [results[v][i] for i in rows] for v, rows in zip(vids, picked) if rows}
+    return out
 
 
 def rows_to_segments(video_rows, shortest=0.2):

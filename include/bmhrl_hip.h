@@ -983,6 +983,29 @@ int bmhrl_proposal_select_soft(const float* pred, int32_t B, int64_t N, const fl
                                int32_t method, float tiou_thresh, float sigma, float min_score, float* props,
                                int32_t* rows, int32_t* count, uint64_t* workspace, int64_t workspace_elems,
                                bmhrl_stream_t stream);
+/* bmhrl_proposal_chain (csrc/event_chain.hip): event-chain selection.  props (B, P, 3) fp32 rows
+ *  [start, end, score] and count (B) int32 are bmhrl_proposal_select's / bmhrl_proposal_select_soft's outputs as they
+ *  stand: the first count[b] rows of video b are valid (count[b] is clamped to [0, P]; count null = all P rows).  All
+ *  arithmetic fp32, uncontracted, in the order written.  Per video:
+ *   eligible  row i < count with (end - start) > min_length, score == score and gain g = score - event_cost > 0
+ *   order     i before j iff (start_i, end_i, i) < (start_j, end_j, j) lexicographically; position = place in it
+ *   link      i -> j iff i before j, end_i <= end_j and t_ij <= max_tiou (t: bmhrl_proposal_select's fp32 tIoU)
+ *   V[1][j] = g_j;  V[l][j] = the maximum over the linked i (in order) with V[l-1][i] defined of
+ *             (V[l-1][i] - (overlap_weight * t_ij)) + g_j, l = 2 .. max_events.  The running maximum starts at -INFINITY
+ *             and a candidate replaces it only when it is greater: the first maximum wins, and a candidate that is NaN
+ *             or -INFINITY (an infinite score or weight) is no candidate.  V[l][j] without a candidate is undefined.
+ *   answer    the largest defined V[l][j], ties to the smaller l, then to the earlier j; the chain is read back through
+ *             the maximising i of every level.
+ *  events (B, max_events, 3) = the chosen rows of props (their bits) in time order, zeros behind; chain (B, max_events)
+ *  int32 = their row indices in props, -1 behind; length (B) int32; value (B) fp32 = the answer's V, 0.f for length 0
+ *  (may be null).  One launch, nothing read back.  -22: a null props / events / chain / length; B outside [1, 65535]; P
+ *  outside [1, BMHRL_PROPOSAL_CHAIN_MAX_P]; max_events outside [1, BMHRL_PROPOSAL_CHAIN_MAX_L]; a NaN or negative
+ *  max_tiou, overlap_weight, event_cost or min_length. */
+#define BMHRL_PROPOSAL_CHAIN_MAX_P 1024
+#define BMHRL_PROPOSAL_CHAIN_MAX_L 32
+int bmhrl_proposal_chain(const float* props, const int32_t* count, int32_t B, int32_t P, int32_t max_events, float max_tiou,
+                         float overlap_weight, float event_cost, float min_length, float* events, int32_t* chain,
+                         int32_t* length, float* value, bmhrl_stream_t stream);
 
 /* ---- segment crop (csrc/segment_crop.hip) --------------------------------------------------------
  * Cuts and pads the rows of P temporal segments out of full-length feature stacks that are resident on the device: the
