@@ -165,6 +165,7 @@ PROTOTYPES = {
     "bmhrl_policy_loss_fwd": [ptr, i64, ptr, ptr, ptr, f32, ptr, ptr, ptr, i64, i32, ptr],
     "bmhrl_policy_loss_bwd": [ptr, i64, ptr, ptr, ptr, f32, ptr, ptr, ptr, ptr, i64, i64, i32, ptr],
     "bmhrl_ngram_stats": [ptr, i32, ptr, i32, ptr, i32, ptr, ptr],
+    "bmhrl_bootstrap_ratios": [ptr, ptr, i32, i32, i32, u64, ptr, ptr],
 }
 
 # QUERIES: name -> (restype, argtypes) of the host-only entries (plans, limits, workspace sizes, build facts): no stream,
@@ -185,6 +186,7 @@ QUERIES = {
     "bmhrl_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(i32)]),
     "bmhrl_gemm_group_plan": (C.c_int, [C.POINTER(GemmDesc), i32]),
     "bmhrl_gemm_f32_fast_path": (C.c_int, [C.POINTER(GemmDesc)]),
+    "bmhrl_bootstrap_rows": (C.c_int, [i32, i32]),
 }
 
 

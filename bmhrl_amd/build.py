@@ -11,7 +11,7 @@ SOURCES = ["gemm.hip", "attention.hip", "attention128.hip", "attention128p.hip",
            "memory_attention.hip", "elementwise.hip", "loss.hip", "critic.hip", "conv_gn.hip", "beam.hip", "rewards.hip", "sample.hip",
            "grad_norm.hip", "constrain.hip", "accum.hip", "consensus.hip", "meteor.hip", "word_loss.hip", "critic_train.hip",
            "caption_eval.hip", "soda.hip", "proposal.hip", "segment_crop.hip", "proposal_eval.hip", "policy_loss.hip",
-           "paragraph.hip", "event_chain.hip"]
+           "paragraph.hip", "event_chain.hip", "bootstrap.hip"]
 HEADERS = ["common.h", "attention_fwd.h", "attention_bwd.h", "attention_pair.h", "meteor_align.h", "caption_text.h", "tiou.h"]
 # attention.hip: the eight 16-register O^T accumulators are loop-carried vector PHIs; AMDGPUCodeGenPrepare would break
 # them into 128 scalar (VGPR) PHIs, i.e. 128 accumulator<->VGPR copies per key tile around the MFMAs.

@@ -70,7 +70,8 @@ def calculate_metrics(reference_paths, submission_path, tIoUs, max_prop_per_vid,
     proposal_recall=True adds AUC and AR@AN; tiou_backend="device" pairs and detects through the device tIoU tables;
     paragraph=True adds the paragraph-level Para_Bleu_1..4, Para_METEOR, Para_ROUGE_L, Para_CIDEr and the repetition /
     diversity figures Para_RE_4, Para_XRE_4, Para_Div_1, Para_Div_2, with paragraph_top=k reading only the k best-scored
-    proposals of a video as its paragraph)."""
+    proposals of a video as its paragraph; bootstrap=R adds the key "Bootstrap intervals": {metric: [dict(value, lo, hi, se)
+    per tIoU]} of R resamples of the videos, evaluate.bootstrap)."""
     fields = ["results", "version", "external_data"]
     if evaluator is None:
         try:
@@ -89,6 +90,8 @@ def calculate_metrics(reference_paths, submission_path, tIoUs, max_prop_per_vid,
     ev.evaluate()
     metrics = {tiou: {name: scores[i] for name, scores in ev.scores.items()} for i, tiou in enumerate(tIoUs)}
     metrics["Average across tIoUs"] = {name: sum(scores) / float(len(scores)) for name, scores in ev.scores.items()}
+    if getattr(ev, "intervals", None):            # the device evaluator ran with bootstrap=R (evaluator_options)
+        metrics["Bootstrap intervals"] = ev.intervals
     return metrics
 
 

@@ -36,6 +36,12 @@ of the predicted paragraphs, from the exact occurrence counts of one ops.ngram_s
 written from the definitions in section 33 and have been compared with no published tool; METEOR is the function above,
 and several ground-truth files are averaged where the usual paragraph protocol takes them as multiple references of one
 score.  So the figures are comparable between runs of this package, not to published paragraph-level numbers.
+
+Bootstrap intervals and run comparison (bootstrap=R; bootstrap, compare, summarize, bootstrap_ratios_host; DESIGN.md
+section 37): .per_video keeps the per-video values every mean over videos is taken of, and the paired bootstrap over
+videos (ops.bootstrap_ratios, csrc/bootstrap.hip: one launch per family; the same definition in numpy when the device is
+the CPU) gives each such figure a percentile interval, and two evaluated runs over the same videos the interval of their
+difference under the same resamples.  It says how much the sample of videos moves a figure, nothing more.
 """
 from __future__ import annotations
 
@@ -382,12 +388,19 @@ class DenseCaptionEvaluator:
     predicted paragraphs: paragraph_groups, paragraph_scores, paragraph_stats, paragraph_means), one
     entry per tIoU, all equal, and .paragraph_per_video (video id -> {"stats": (4, 5) int32 total, distinct, in_repeated,
     cross, max_count per n, "sentences", "tokens"}).  paragraph_top=k reads only the k best-scored proposals of a video
-    (by_proposal_score) as its paragraph; None reads all.  sort_references applies to the reference paragraphs too."""
+    (by_proposal_score) as its paragraph; None reads all.  sort_references applies to the reference paragraphs too.
+    .per_video (after .evaluate(), not only_proposals) keeps the per-video values the means were taken of: family ->
+    (video ids, {metric: [fp64 array per tIoU]}) for "tiou" (the seven METRICS over tokenized_pairs' videos), "soda" (the
+    SODA_METRICS over .soda_per_video's videos) and "paragraph" (Para_RE_4 / Para_XRE_4 / Para_Div_1 / Para_Div_2 as (2, N)
+    arrays of value and weight: paragraph_values).  bootstrap=R: .evaluate() also fills .intervals = bootstrap(self, R,
+    bootstrap_seed, bootstrap_alpha) below, {metric: [dict(value, lo, hi, se) per tIoU]} (what is
+    out of its scope: see bootstrap).  .scores and the printed lines are the same with and without it."""
 
     def __init__(self, ground_truth_filenames=None, prediction_filename=None, tious=None, max_proposals=1000,
                  prediction_fields=PREDICTION_FIELDS, verbose=False, only_proposals=False, *, device="cuda",
                  tokenizer: Callable[[str], List[str]] = tokenize, stemmer=None, synonyms=None, soda=False,
-                 sort_references=False, tiou_backend="host", proposal_recall=False, paragraph=False, paragraph_top=None):
+                 sort_references=False, tiou_backend="host", proposal_recall=False, paragraph=False, paragraph_top=None,
+                 bootstrap=None, bootstrap_seed=0, bootstrap_alpha=0.05):
         if tious is None or len(tious) == 0:
             raise IOError("Please input a valid tIoU.")
         if not ground_truth_filenames:
@@ -413,6 +426,15 @@ class DenseCaptionEvaluator:
             raise ValueError(f"paragraph_top {paragraph_top!r}: a positive integer or None expected")
         self.paragraph, self.paragraph_top = bool(paragraph), None if paragraph_top is None else int(paragraph_top)
         self.paragraph_per_video: Dict[str, dict] = {}
+        if bootstrap is not None and (isinstance(bootstrap, bool) or not isinstance(bootstrap, (int, np.integer))
+                                      or bootstrap < 1):
+            raise ValueError(f"bootstrap {bootstrap!r}: a positive number of resamples or None expected")
+        if not 0.0 < bootstrap_alpha < 1.0:
+            raise ValueError(f"bootstrap_alpha {bootstrap_alpha!r}: a number in (0, 1) expected")
+        self.bootstrap = None if bootstrap is None else int(bootstrap)
+        self.bootstrap_seed, self.bootstrap_alpha = int(bootstrap_seed), float(bootstrap_alpha)
+        self.per_video: Dict[str, tuple] = {}
+        self.intervals: Dict[str, List[dict]] = {}
         self._tables = self._detection = self._table_tokens = None
         self.ground_truths = self.import_ground_truths(ground_truth_filenames)
         self.prediction = self.import_prediction(prediction_filename)
@@ -456,14 +478,24 @@ class DenseCaptionEvaluator:
     # ---- scoring
     def evaluate(self) -> None:
         self.scores = {}
+        self.per_video, self.intervals = {}, {}
         if not self.only_proposals:
+            vids, kept = [], {m: [] for m in METRICS}
             for t in self.tious:
-                for metric, score in self.evaluate_tiou(t).items():
+                out, vids, values = self.tiou_scores(t)
+                for metric, score in out.items():
                     self.scores.setdefault(metric, []).append(score)
+                for m in METRICS:
+                    kept[m].append(values[m])
+            self.per_video["tiou"] = (vids, kept)
             if self.soda:
                 self.scores.update(self.evaluate_soda())
+                self.per_video["soda"] = soda_values(self.soda_per_video, len(self.tious))
             if self.paragraph:
                 self.scores.update(self.evaluate_paragraph())
+                self.per_video["paragraph"] = paragraph_values(self.paragraph_per_video, len(self.tious))
+            if self.bootstrap is not None:
+                self.intervals = bootstrap(self, self.bootstrap, self.bootstrap_seed, self.bootstrap_alpha)
         if self.verbose:
             self.scores["Recall"], self.scores["Precision"] = [], []
             for t in self.tious:
@@ -528,15 +560,20 @@ class DenseCaptionEvaluator:
         return list(tables.vids), off, hyps, refs
 
     def evaluate_tiou(self, tiou_threshold) -> Dict[str, float]:
+        return self.tiou_scores(tiou_threshold)[0]
+
+    def tiou_scores(self, tiou_threshold):
+        """(evaluate_tiou's dictionary, the video ids, {metric: (N,) fp64 per-video values}): the means of a threshold and
+        what they were taken of, over tokenized_pairs' video list"""
         vids, off, hyps, refs = self.tokenized_pairs(tiou_threshold)
         if not hyps:                           # nothing was predicted for any ground-truth video: every video scores 0
-            return {m: 0.0 for m in METRICS}
+            return {m: 0.0 for m in METRICS}, vids, {m: np.zeros(len(vids), dtype=np.float64) for m in METRICS}
         per_video = score_pairs(hyps, refs, off, self.device, self.meteor_tables())
         out = {m: float(np.mean(per_video[m])) for m in METRICS}
         if self.verbose:
             for m in METRICS:
                 print("Calculated tIoU: %1.1f, %s: %0.3f" % (tiou_threshold, m, out[m]))
-        return out
+        return out, vids, {m: np.asarray(per_video[m], dtype=np.float64) for m in METRICS}
 
     def evaluate_soda(self) -> Dict[str, List[float]]:
         """SODA_c, SODA_c_Precision, SODA_c_Recall per tIoU and .soda_per_video"""
@@ -951,4 +988,247 @@ def paragraph_means(stats: np.ndarray) -> Dict[str, float]:
                           ("Para_Div_1", 1, lambda r: r[1] / r[0]), ("Para_Div_2", 2, lambda r: r[1] / r[0])):
         vals = [value([int(x) for x in row]) for row in stats[:, n - 1] if row[0] > 0]
         out[key] = sum(vals) / len(vals) if vals else 0.0
+    return out
+
+
+# ---- bootstrap intervals and paired run comparison
+PARAGRAPH_STAT_KEYS = ("Para_RE_4", "Para_XRE_4", "Para_Div_1", "Para_Div_2")
+_BOOT_CHUNK = 1 << 22                         # count cells (resamples x videos) per pass of bootstrap_ratios_host
+_U64 = np.uint64
+BOOTSTRAP_LIMITS = (16384, 4096, 1 << 20)     # videos, columns, resamples: ops.BOOTSTRAP_MAX_N / _M / _R
+
+
+def _hash_u32(seed: int, idx: np.ndarray) -> np.ndarray:
+    """csrc/common.h's hash_u32 over a uint64 array (the arithmetic wraps modulo 2^64, as the device's)"""
+    z = idx * _U64(0x9E3779B97F4A7C15) + _U64(seed)
+    z = (z ^ (z >> _U64(30))) * _U64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> _U64(27))) * _U64(0x94D049BB133111EB)
+    z = z ^ (z >> _U64(31))
+    return z >> _U64(32)
+
+
+def bootstrap_counts(N: int, rows: Sequence[int], seed: int) -> np.ndarray:
+    """(len(rows), N) int64: the counts c_i of the rows `rows` of the bootstrap's definition -- all ones for row 0, and for
+    row r >= 1 the number of the N draws i = (hash_u32(seed, (r << 32) | j) * N) >> 32, j = 0 .. N - 1, that hit video i"""
+    rows = np.asarray(rows, dtype=np.uint64).reshape(-1)
+    idx = (rows[:, None] << _U64(32)) | np.arange(N, dtype=np.uint64)[None, :]
+    drawn = ((_hash_u32(seed, idx) * _U64(N)) >> _U64(32)).astype(np.int64)
+    flat = drawn + (np.arange(len(rows), dtype=np.int64) * N)[:, None]
+    counts = np.bincount(flat.reshape(-1), minlength=len(rows) * N).reshape(len(rows), N)
+    counts[rows == 0] = 1
+    return counts
+
+
+def _check_bootstrap_inputs(values, weights, resamples, seed, limits):
+    if values.ndim != 2 or (weights is not None and weights.shape != values.shape):
+        raise ValueError("bootstrap: values (M, N) and weights (M, N) or None expected")
+    M, N = values.shape
+    max_n, max_m, max_r = limits
+    if not (1 <= N <= max_n and 1 <= M <= max_m and 1 <= resamples <= max_r):
+        raise ValueError(f"bootstrap: {N} videos, {M} columns, {resamples} resamples; at most {max_n}, {max_m}, {max_r} "
+                         "and at least one of each are supported")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"bootstrap: seed {seed} is no uint64")
+
+
+def bootstrap_ratios_host(values, weights, resamples: int, seed: int = 0) -> np.ndarray:
+    """ops.bootstrap_ratios in numpy, bit for bit (B1-B4 of bmhrl_bootstrap_ratios, include/bmhrl_hip.h): values (M, N)
+    fp64, weights (M, N) fp64 or None -> stats (resamples + 1, M) fp64.  The hash is uint64 array arithmetic; the 64 lane
+    sums run over the ceil(N / 64) strides in ascending order, vectorised over resamples, columns and lanes, product and sum
+    as two numpy operations (two roundings); the butterfly adds the two halves of the lane axis six times.  Non-finite
+    inputs are a ValueError.  The route of evaluate.bootstrap / compare when the evaluator's device is the CPU."""
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    R, seed = int(resamples), int(seed)
+    _check_bootstrap_inputs(values, weights, R, seed, BOOTSTRAP_LIMITS)
+    if not np.isfinite(values).all() or (weights is not None and not np.isfinite(weights).all()):
+        raise ValueError("bootstrap: non-finite values or weights")
+    M, N = values.shape
+    stats = np.empty((R + 1, M), dtype=np.float64)
+    strides = -(-N // 64)
+
+    def padded(a):                              # (M, strides, 64): lane t of stride k is video 64 k + t
+        out = np.zeros((M, strides * 64), dtype=np.float64)
+        out[:, :N] = a
+        return out.reshape(M, strides, 64)
+
+    def lane_sums(c, a):                        # c (rows, strides, 64) fp64, a (M, strides, 64) -> S (rows, M), B2 and B3
+        p = np.zeros((c.shape[0], M, 64), dtype=np.float64)
+        last = N - (strides - 1) * 64           # the lanes of the last stride that hold a video
+        for k in range(strides):
+            n = 64 if k < strides - 1 else last
+            p[:, :, :n] = p[:, :, :n] + (c[:, None, k, :n] * a[None, :, k, :n])
+        for s in (32, 16, 8, 4, 2, 1):
+            p = p + p.reshape(-1, M, 64 // (2 * s), 2, s)[:, :, :, ::-1, :].reshape(-1, M, 64)
+        return p[:, :, 0]
+
+    x = padded(values)
+    w = None if weights is None else padded(weights)
+    step = max(1, _BOOT_CHUNK // (max(M, 1) * strides * 64))
+    for lo in range(0, R + 1, step):
+        rows = np.arange(lo, min(lo + step, R + 1))
+        c = np.zeros((len(rows), strides * 64), dtype=np.float64)
+        c[:, :N] = bootstrap_counts(N, rows, seed)
+        c = c.reshape(len(rows), strides, 64)
+        num = lane_sums(c, x)
+        if w is None:
+            stats[rows] = num / np.float64(N)
+        else:
+            den = lane_sums(c, w)
+            zero = den == 0.0
+            stats[rows] = np.where(zero, 0.0, num / np.where(zero, 1.0, den))
+    return stats
+
+
+def soda_values(per_video: Dict[str, List[Tuple[float, float, float]]], T: int):
+    """(video ids, {metric: [(N,) fp64 per tIoU]}) of .soda_per_video: the values soda_means takes its means of, in its
+    order of the videos"""
+    vids = list(per_video)
+    return vids, {m: [np.array([per_video[v][t][c] for v in vids], dtype=np.float64) for t in range(T)]
+                  for m, c in zip(SODA_METRICS, (2, 0, 1))}
+
+
+def paragraph_values(per_video: Dict[str, dict], T: int):
+    """(video ids, {key: [(2, N) fp64 per tIoU]}) of .paragraph_per_video for PARAGRAPH_STAT_KEYS: row 0 a video's ratio
+    (paragraph_means' expressions) or 0.0, row 1 its weight, 1.0 where the video's total at the key's n is > 0, else 0.0.
+    The mean of the weighted videos is paragraph_means' figure; the T entries of a key are one array."""
+    vids = list(per_video)
+    out = {}
+    for key, n, value in (("Para_RE_4", 4, lambda r: (r[0] - r[1]) / r[0]), ("Para_XRE_4", 4, lambda r: r[3] / r[0]),
+                          ("Para_Div_1", 1, lambda r: r[1] / r[0]), ("Para_Div_2", 2, lambda r: r[1] / r[0])):
+        col = np.zeros((2, len(vids)), dtype=np.float64)
+        for v, vid in enumerate(vids):
+            row = [int(x) for x in per_video[vid]["stats"][n - 1]]
+            if row[0] > 0:
+                col[0, v], col[1, v] = value(row), 1.0
+        out[key] = [col] * T
+    return vids, out
+
+
+def summarize(stats, alpha: float = 0.05):
+    """(lo, hi, se), each (M,): the percentile interval and the standard error of the resampled rows 1 .. R of stats
+    (R + 1, M) -- a torch tensor (sorted by torch.sort where it lives) or a numpy array (np.sort).  Per column over the R
+    values sorted ascending: lo = sorted[clamp(int(floor(alpha / 2 * R)))], hi = sorted[clamp(int(ceil((1 - alpha / 2) * R))
+    - 1)], the indices clamped to [0, R - 1]; se = their unbiased standard deviation (0.0 for R = 1).  Row 0, the observed
+    statistic, is not read.  Returns what it was given: tensors for a tensor, arrays for an array."""
+    import math
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"alpha {alpha!r}: a number in (0, 1) expected")
+    R = stats.shape[0] - 1
+    if stats.ndim != 2 or R < 1:
+        raise ValueError("summarize: stats (R + 1, M) with R >= 1 expected")
+    clamp = lambda k: min(max(k, 0), R - 1)                                                                 # noqa: E731
+    i_lo, i_hi = clamp(int(math.floor(alpha / 2 * R))), clamp(int(math.ceil((1 - alpha / 2) * R)) - 1)
+    if isinstance(stats, np.ndarray):
+        s = np.sort(stats[1:], axis=0)
+        se = s.std(axis=0, ddof=1) if R > 1 else np.zeros(stats.shape[1], dtype=stats.dtype)
+        return s[i_lo].copy(), s[i_hi].copy(), se
+    import torch
+    s = torch.sort(stats[1:], dim=0).values
+    se = s.std(dim=0, unbiased=True) if R > 1 else torch.zeros_like(s[0])
+    return s[i_lo].clone(), s[i_hi].clone(), se
+
+
+def _family_columns(evaluator, family: str):
+    """(video ids, [(metric, tIoU index)] per column, values (M, N), weights (M, N) or None) of one family of
+    evaluator.per_video; the paragraph family carries weights, and its tIoU entries are one column each all the same"""
+    vids, metrics = evaluator.per_video[family]
+    names, cols, wts = [], [], []
+    for m, per_tiou in metrics.items():
+        for t, col in enumerate(per_tiou):
+            names.append((m, t))
+            if family == "paragraph":
+                cols.append(col[0])
+                wts.append(col[1])
+            else:
+                cols.append(col)
+    values = np.asarray(cols, dtype=np.float64).reshape(len(cols), len(vids))
+    weights = np.asarray(wts, dtype=np.float64).reshape(len(cols), len(vids)) if family == "paragraph" else None
+    return vids, names, values, weights
+
+
+def _evaluated(evaluator, what):
+    per_video = getattr(evaluator, "per_video", None)
+    if not per_video:
+        raise ValueError(f"{what}: an evaluator after .evaluate() (and not only_proposals) expected")
+    return per_video
+
+
+def _stats_on(values, weights, resamples, seed, device):
+    """the (R + 1, M) statistics where `device` says: a device tensor from the launch, or the host route's array"""
+    import torch
+    if torch.device(device).type == "cpu":
+        return bootstrap_ratios_host(values, weights, resamples, seed)
+    from . import ops
+    for a in (values, weights):
+        if a is not None and not np.isfinite(a).all():
+            raise ValueError("bootstrap: non-finite values or weights")
+    dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device)             # noqa: E731
+    return ops.bootstrap_ratios(dev(values), dev(weights), int(resamples), int(seed))
+
+
+def _host(x) -> np.ndarray:
+    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
+
+
+def bootstrap(evaluator, resamples: int = 10000, seed: int = 0, alpha: float = 0.05) -> Dict[str, List[dict]]:
+    """{metric: [dict(value, lo, hi, se) per tIoU]}: the paired bootstrap over videos (Koehn 2004) of every figure of an
+    evaluated DenseCaptionEvaluator that is a mean over videos -- the seven METRICS, the SODA_METRICS with soda=True,
+    Para_RE_4 / Para_XRE_4 / Para_Div_1 / Para_Div_2 with paragraph=True.  One bootstrap_ratios call per family of
+    evaluator.per_video (their video lists can differ), on evaluator.device (the CPU runs bootstrap_ratios_host: the same
+    bits), then summarize.  `value` is evaluator.scores' entry, not row 0 of the call; lo / hi are the 1 - alpha percentile
+    interval of the resampled means, se their standard deviation.
+
+    Out of scope: Para_Bleu_* .. Para_CIDEr (corpus-level per ground-truth file), Precision / Recall, AUC and AR@AN (not
+    means over videos).  The corpus BLEU within a video stays as it is: the video is the resampling unit.  No
+    multiple-comparison correction.  The interval says how much the sample of videos moves a figure; it says nothing about
+    how close this package's stand-in METEOR is to published numbers."""
+    out: Dict[str, List[dict]] = {}
+    for family in _evaluated(evaluator, "bootstrap"):
+        vids, names, values, weights = _family_columns(evaluator, family)
+        if not names or not len(vids):
+            continue
+        lo, hi, se = (_host(a) for a in summarize(_stats_on(values, weights, resamples, seed, evaluator.device), alpha))
+        for c, (m, t) in enumerate(names):
+            out.setdefault(m, []).append({"value": float(evaluator.scores[m][t]), "lo": float(lo[c]), "hi": float(hi[c]),
+                                          "se": float(se[c])})
+    return out
+
+
+def compare(evaluator_a, evaluator_b, resamples: int = 10000, seed: int = 0, alpha: float = 0.05) -> Dict[str, List[dict]]:
+    """{metric: [dict(a, b, delta, lo, hi, wins, losses) per tIoU]}: two evaluated runs over the same videos under one
+    resample.  Per family the columns of A and of B go into ONE (2 M, N) bootstrap_ratios call (on evaluator_a.device), so
+    both runs see the same counts; delta_r = stat_A[r] - stat_B[r]; a / b are the two .scores entries and delta = a - b;
+    lo / hi the percentile interval of delta over the resamples (summarize); wins the share of resamples with delta > 0,
+    losses the share with delta < 0.  The families, metrics and tIoUs of the two evaluators must be the same and their
+    video-id lists equal: otherwise a ValueError, naming the first differing id.  bootstrap's out-of-scope list applies:
+    only means over videos, no multiple-comparison correction, nothing about published figures."""
+    pa, pb = _evaluated(evaluator_a, "compare"), _evaluated(evaluator_b, "compare")
+    if list(pa) != list(pb):
+        raise ValueError(f"compare: the evaluators hold different families: {list(pa)} and {list(pb)}")
+    out: Dict[str, List[dict]] = {}
+    for family in pa:
+        vids_a, names_a, values_a, weights_a = _family_columns(evaluator_a, family)
+        vids_b, names_b, values_b, weights_b = _family_columns(evaluator_b, family)
+        if list(vids_a) != list(vids_b):
+            k = next((k for k, (u, v) in enumerate(zip(vids_a, vids_b)) if u != v), min(len(vids_a), len(vids_b)))
+            first = vids_a[k] if k < len(vids_a) else None
+            other = vids_b[k] if k < len(vids_b) else None
+            raise ValueError(f"compare: the {family} video lists differ at position {k}: {first!r} and {other!r}")
+        if names_a != names_b:
+            raise ValueError(f"compare: the evaluators hold different {family} metrics or tIoUs")
+        if not names_a or not len(vids_a):
+            continue
+        M = len(names_a)
+        values = np.concatenate([values_a, values_b])
+        weights = None if weights_a is None else np.concatenate([weights_a, weights_b])
+        stats = _stats_on(values, weights, resamples, seed, evaluator_a.device)
+        delta = stats[:, :M] - stats[:, M:]
+        lo, hi, _ = (_host(a) for a in summarize(delta, alpha))
+        d = _host(delta[1:])
+        wins, losses = (d > 0).sum(axis=0) / float(d.shape[0]), (d < 0).sum(axis=0) / float(d.shape[0])
+        for c, (m, t) in enumerate(names_a):
+            a, b = float(evaluator_a.scores[m][t]), float(evaluator_b.scores[m][t])
+            out.setdefault(m, []).append({"a": a, "b": b, "delta": a - b, "lo": float(lo[c]), "hi": float(hi[c]),
+                                          "wins": float(wins[c]), "losses": float(losses[c])})
     return out

@@ -894,6 +894,44 @@ def ngram_stats(tok, sent_off, para_off):
     return stats
 
 
+# ---- bootstrap over videos (csrc/bootstrap.hip)
+BOOTSTRAP_MAX_N, BOOTSTRAP_MAX_M, BOOTSTRAP_MAX_R = 16384, 4096, 1 << 20      # BMHRL_BOOTSTRAP_MAX_N / _M / _R
+
+
+def _f64c(t, shape, what):
+    if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous fp64 tensor of shape {tuple(shape)}")
+
+
+def bootstrap_rows(N, resamples):
+    """the rows of the output one workgroup of bootstrap_ratios carries at N videos (bmhrl_bootstrap_rows): what the
+    benchmark needs to count the bytes the launch reads"""
+    return _query("bmhrl_bootstrap_rows", int(N), int(resamples))
+
+
+def bootstrap_ratios(values, weights, resamples, seed=0):
+    """(resamples + 1, M) fp64: row 0 the observed statistic of every column, row r >= 1 that of resample r of the N videos;
+    see bmhrl_bootstrap_ratios in include/bmhrl_hip.h (csrc/bootstrap.hip).  values (M, N) fp64 -- a column's N per-video
+    values are contiguous -- and weights (M, N) fp64 or None: the statistic is sum(c * x) / sum(c * w) (0.0 for a zero
+    denominator), without weights sum(c * x) / N, c the resample's counts (all 1 in row 0), drawn from hash_u32(seed, .).
+    N <= BOOTSTRAP_MAX_N, M <= BOOTSTRAP_MAX_M, 1 <= resamples <= BOOTSTRAP_MAX_R; the inputs are finite (the callers in
+    evaluate.py check).  One launch, nothing read back."""
+    if values.dim() != 2:
+        raise ValueError("bootstrap_ratios: values (M, N) expected")
+    M, N = values.shape
+    _f64c(values, (M, N), "bootstrap_ratios (values)")
+    if weights is not None:
+        _f64c(weights, (M, N), "bootstrap_ratios (weights)")
+        if weights.device != values.device:
+            raise ValueError("bootstrap_ratios: values and weights on one device expected")
+    R, seed = int(resamples), int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"bootstrap_ratios: seed {seed} is no uint64")
+    stats = torch.empty(max(R, 0) + 1, M, dtype=torch.float64, device=values.device)
+    _launch("bmhrl_bootstrap_ratios", values, weights, N, M, R, seed, stats)
+    return stats
+
+
 # ---- SODA_c: the all-pairs METEOR matrix and the ordered assignment (csrc/soda.hip)
 SODA_MAX_REFS, SODA_MAX_T = 256, 16          # BMHRL_SODA_MAX_REFS / _T of include/bmhrl_hip.h
 

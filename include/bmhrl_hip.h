@@ -1150,6 +1150,32 @@ int bmhrl_policy_loss_bwd(const float* logp, int64_t ld, const int64_t* action, 
 int bmhrl_ngram_stats(const int32_t* tok, int32_t n_tok, const int32_t* sent_off, int32_t S, const int32_t* para_off,
                       int32_t G, int32_t* stats, bmhrl_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Bootstrap over videos (csrc/bootstrap.hip; bmhrl_amd/evaluate.py bootstrap_ratios_host is the same definition in numpy;
+ * DESIGN.md section 37).  values (M, N) fp64: column m's N per-video values are contiguous.  weights (M, N) fp64 or null.
+ * stats (resamples + 1, M) fp64.  All arithmetic fp64, uncontracted, in the order written.
+ *  B1. Counts.  Row 0 is the observed statistic: c_i = 1 for every i.  Row r >= 1 makes N draws j = 0 .. N - 1:
+ *      h = hash_u32(seed, ((uint64)r << 32) | j) (csrc/common.h), i = (uint32)(((uint64)h * N) >> 32), and c_i is the number
+ *      of draws that hit i.  Integers: no order enters, and the c_i sum to N.
+ *  B2. Lane sums.  For a column m and a lane t = 0 .. 63, p_t starts at +0.0 and for i = t, t + 64, .. < N in ascending
+ *      order p_t = p_t + ((double)c_i * x[m][i]): two roundings per term, every term added, those with c_i = 0 too.
+ *  B3. Butterfly.  For s = 32, 16, 8, 4, 2, 1: p_t = p_t + p_(t xor s).  Every lane ends with the same bits, S_num.
+ *  B4. Statistic.  With weights S_den is formed the same way from w[m][i] and stats[r][m] = S_num / S_den, or 0.0 when
+ *      S_den == 0; without weights stats[r][m] = S_num / (double)N.
+ *  The result depends on nothing else: not the grid, the split of the columns or the rows a workgroup carries.  Nothing is
+ *  promised for non-finite inputs.  One launch, no global atomics, nothing read back.
+ *  -22: a null values / stats; N outside [1, BMHRL_BOOTSTRAP_MAX_N]; M outside [1, BMHRL_BOOTSTRAP_MAX_M]; resamples
+ *  outside [1, BMHRL_BOOTSTRAP_MAX_R].
+ * ------------------------------------------------------------------------------------------- */
+#define BMHRL_BOOTSTRAP_MAX_N 16384
+#define BMHRL_BOOTSTRAP_MAX_M 4096
+#define BMHRL_BOOTSTRAP_MAX_R 1048576
+int bmhrl_bootstrap_ratios(const double* values, const double* weights, int32_t N, int32_t M, int32_t resamples, uint64_t seed,
+                           double* stats, bmhrl_stream_t stream);
+/* the rows of stats one workgroup of that launch carries (4, 2 or 1: the most whose counts fit its LDS budget); -22 for an
+ * N or a number of resamples the launch refuses.  Host only; the result of the launch does not depend on it. */
+int bmhrl_bootstrap_rows(int32_t N, int32_t resamples);
+
 int bmhrl_hip_abi_version(void);
 /* 1 when BMHRL_DETERMINISTIC selects the ordered sums (read once, by the library; atoi(value) != 0).  The host side asks
  * here instead of parsing the variable itself, so both sides always agree. */
